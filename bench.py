@@ -8,6 +8,14 @@ defaults), then the download of what the controller publishes (us[0], K[0], x1 a
 Inputs sit in HBM before the timed region starts.
 
   python bench.py [--gpus N --steps K --warmup W --batch B --horizon T --max-iter I --workload W --scaling weak|strong]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything else after the
+timed region: in-situ per-kernel times and the roofline, the extra legs (batch 1 / 128 latency, disturbed, max_iter 3,
+quorum 0.985, full download, host refs) and the CPU baseline.  --dump-outputs DIR writes what the last timed step handed
+to its caller (us[0], K[0], x1 and the status words of every instance) as DIR/<name>.npy in float64, at most 64 MB (a
+seeded sample of the instances beyond that, their indices in DIR/instance_index.npy); the inputs depend on the
+arguments only, so two builds can be compared output for output.
 
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL).  Instances are
 independent, so ranks share nothing while they solve: the collectives are the barriers, the MAX over ranks of the
@@ -92,8 +100,13 @@ def parse():
                          "carry their iterate into the next step unsolved (as a lone controller hitting max_solve_time).  Default 1.0 "
                          "(everyone, as the CPU baseline and upstream); the collision / cartesian workloads report the 0.985 policy in "
                          "an extra leg (`quorum_0985`), never as `value`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-batch1", action="store_true", help="skip the extra legs (batch 1 latency, max_iter 3, full download, host refs): profiling runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel times / roofline, the extra legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the first-node results and status words of the last timed step as DIR/<name>.npy (float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-batch1", action="store_true", help="with --full: skip the extra legs (batch 1 latency, max_iter 3, full download, "
+                                                             "host refs): profiling runs")
     ap.add_argument("--cpu-instances", type=int, default=0, help="instances of the CPU sample (0 = 2 per core, at most 256)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU work the baseline sample is sized for")
     ap.add_argument("--loop", choices=("prediction", "feedback"), default="prediction",
@@ -108,6 +121,8 @@ def parse():
                          "humanoid: configs[4] synthetic 30-DoF tree (T 50, B 512); collision / cartesian: configs[2], collision-avoidance cost "
                          "+ distance constraint (T 200, B 256) with configuration-space / cartesian sine references")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     shape = {"collision": (256, 200), "cartesian": (256, 200), "humanoid": (512, 50)}.get(args.workload, (1024, 100))
     if args.batch is None:
         args.batch = shape[0]
@@ -209,6 +224,33 @@ def disturbance_noise(B, n_steps, nv, sigma, seed0):
         out[b, :, :nv] = rng.normal(0.0, sigma, (n_steps, nv))
         out[b, :, nv:] = rng.normal(0.0, 5.0 * sigma, (n_steps, nv))
     return out
+
+
+DUMP_LIMIT = 64_000_000  # bytes written by --dump-outputs in all
+
+
+def first_node_outputs(res):
+    """What one MPC step hands to its caller (download_first: us[0], K[0], x1, status words) as float64 copies."""
+    us0, K0, x1, st = res
+    out = {"us0": us0, "K0": K0, "x1": x1}
+    out.update((f"status_{name}", v) for name, v in st.items())
+    return {name: np.array(a, dtype=np.float64) for name, a in out.items()}
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays [n_instances, ...] as out_dir/<name>.npy.  Above DUMP_LIMIT a sample of the instances drawn with a fixed seed
+    (the same for every run of the same arguments); their indices go to instance_index.npy."""
+    d = pathlib.Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    per = sum(a[0].nbytes for a in arrays.values())
+    budget = DUMP_LIMIT - 256 * (len(arrays) + 1)  # .npy headers
+    if per * n > budget:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=max(1, budget // (per + 8)), replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["instance_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
 
 
 def _cpu_leg(args, table, po, refs: HostRefs, seconds, analytic, noise=None):
@@ -404,13 +446,20 @@ def main():
     sync_all()
     t_start = time.perf_counter()
     for k in range(args.warmup, args.warmup + args.steps):
-        st = step(k)[3]
+        res = step(k)
+        st = res[3]
         iters.append(float(st["iter"].mean()))
         iters_max.append(int(st["iter"].max()))
         if k % 8 == 0:
             solved_hist.append(float(np.asarray(st["solved"]).mean()))
     sync_all()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs:
+        outs = first_node_outputs(res)  # copies: the views of `res` are overwritten by the next step
+        if dist is not None:
+            outs = {name: batched.gather_rows(a, global_batch, device=coll_dev) for name, a in outs.items()}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
     solved_hist.append(float(np.asarray(st["solved"]).mean()))
     solved_local = np.asarray(st["solved"], dtype=np.float64).copy()
     iter_local = np.asarray(st["iter"], dtype=np.float64).copy()
@@ -432,12 +481,12 @@ def main():
         solved_frac, status_ranks = float(allst[valid, 0].mean()), world
         assert int(valid.sum()) == global_batch, (int(valid.sum()), global_batch)
 
-    # per-kernel device time, measured live and in situ: a few more MPC steps of the same loop with
+    # --full: per-kernel device time, measured live and in situ: a few more MPC steps of the same loop with
     # HIP events around every launch on the solver's stream (outside the timed region above)
     kernels = {}
     k_next = args.warmup + args.steps
     n_prof = min(10, T // 2)
-    if rank == 0:
+    if args.full and rank == 0:
         # the large-model derivative kernel takes running and terminal nodes in one launch
         nodes = {"calc_qp": B * (T + 1) if nv > 8 else B * T, "riccati": B * (T + 1), "step": B * (T + 1)}
         ALGO = algo_doubles(nv)
@@ -450,27 +499,14 @@ def main():
             algo = ALGO[name] * 8 * nodes[name]
             kernels[name] = {"ms": ms, "launches": cnt[i], "algorithmic_bytes": algo, "GBps": algo / (ms * 1e-3) / 1e9,
                              "frac_hbm": algo / (ms * 1e-3) / HBM_PEAK}
-    else:
+    elif args.full:
         for k in range(k_next, k_next + n_prof):
             step(k)
     k_next += n_prof
 
     result = None
-    extra = world == 1 and not args.no_batch1
+    extra = args.full and world == 1 and not args.no_batch1
     if rank == 0:
-        k1 = kernels["calc_qp"]
-        # HBM bytes from separate rocprofv3 --pmc passes (scripts/collect_profiles.sh), committed under profiles/:
-        # never measured by this run
-        traffic, step_traffic, tsrc = None, None, None
-        tfile = ROOT / "profiles" / "pmc_traffic.json"
-        if tfile.exists():
-            try:
-                doc = json.loads(tfile.read_text())
-                traffic = doc.get(f"{K1_NAME[args.workload].replace('_coll', '')}:{args.workload},B={B},T={T}")
-                step_traffic = doc.get(f"step:{args.workload},B={B},T={T}")
-                tsrc = doc.get("_source")
-            except Exception:
-                traffic = None
         ms_step = elapsed / args.steps * 1e3
         result = {
             "metric": f"MPC steps/sec (horizon={T}, Panda 7-DoF)",
@@ -504,7 +540,22 @@ def main():
                 "solved_fraction_mean": float(np.mean(solved_hist)),  # every 8th step of the timed region
                 "step_includes": "window select, x0<-xs[1], warm-start shift, SQP solve, D2H of us[0],K[0],x1,status",
             },
-            "roofline": {
+        }
+        if args.full:
+            k1 = kernels["calc_qp"]
+            # HBM bytes from separate rocprofv3 --pmc passes (scripts/collect_profiles.sh), committed under profiles/:
+            # never measured by this run
+            traffic, step_traffic, tsrc = None, None, None
+            tfile = ROOT / "profiles" / "pmc_traffic.json"
+            if tfile.exists():
+                try:
+                    doc = json.loads(tfile.read_text())
+                    traffic = doc.get(f"{K1_NAME[args.workload].replace('_coll', '')}:{args.workload},B={B},T={T}")
+                    step_traffic = doc.get(f"step:{args.workload},B={B},T={T}")
+                    tsrc = doc.get("_source")
+                except Exception:
+                    traffic = None
+            result["roofline"] = {
                 "kernel": K1_TEXT[K1_NAME[args.workload]],
                 "bound": "hbm",
                 "achieved": k1["GBps"],
@@ -515,14 +566,13 @@ def main():
                 "traffic_source": ((tsrc or "profiles/pmc_traffic.json") + " (separate rocprofv3 --pmc passes, not measured by this run)") if traffic else None,
                 "avg_launch_ms": k1["ms"],
                 "algorithmic_bytes_per_launch": k1["algorithmic_bytes"],
-            },
-            "kernels": kernels,
-        }
-        if step_traffic:
-            # all kernels of one MPC step: counter bytes (profiles/) over the step time of THIS run
-            result["roofline_step"] = {"traffic_per_step": step_traffic, "GBps": step_traffic / (ms_step * 1e-3) / 1e9,
-                                       "frac": step_traffic / (ms_step * 1e-3) / HBM_PEAK,
-                                       "note": "HBM bytes of every kernel of one MPC step (profiles/, WRITE_SIZE + 2 FETCH_SIZE) / ms_per_step of this run"}
+            }
+            result["kernels"] = kernels
+            if step_traffic:
+                # all kernels of one MPC step: counter bytes (profiles/) over the step time of THIS run
+                result["roofline_step"] = {"traffic_per_step": step_traffic, "GBps": step_traffic / (ms_step * 1e-3) / 1e9,
+                                           "frac": step_traffic / (ms_step * 1e-3) / HBM_PEAK,
+                                           "note": "HBM bytes of every kernel of one MPC step (profiles/, WRITE_SIZE + 2 FETCH_SIZE) / ms_per_step of this run"}
         if args.workload in ("collision", "cartesian"):
             result["metric"] = f"MPC steps/sec (horizon={T}, Panda 7-DoF, collision avoidance)"
         if args.workload == "humanoid":
@@ -677,9 +727,9 @@ def main():
     # from the host (agx_ocp_set_refs: H2D of [B][T+1][stride]), then shift + solve + download of the first-node results.
     # With N > 1 ranks the tiles of the whole job originate on rank 0 and travel through batched.scatter_rows (RCCL
     # point-to-point), the first-node results go back through gather_rows: the data-path payload of SURVEY 8(e).
-    host_leg = not args.no_batch1
+    host_leg = args.full and not args.no_batch1
     n_cpu = args.cpu_instances or min(2 * ncores(), 256, B)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     refs = None
     if host_leg:
         refs = HostRefs(hip, po, w, min(n_points, max(k_next + T + 16, T + 1 + 64)), B)

@@ -36,7 +36,7 @@ def main():
     for w in sys.argv[1:]:
         src = ROOT / "gpurun_out" / f"prof_{w}"
         B, T = SHAPE[w]
-        cmd = f"AGX_NO_EMPTY_LAUNCHES=1 AGX_K1_FUSED=0 rocprofv3 --kernel-trace --stats -- python3 bench.py --workload {w} --no-cpu-baseline --no-batch1 --steps 20 --warmup 3"
+        cmd = f"AGX_NO_EMPTY_LAUNCHES=1 AGX_K1_FUSED=0 rocprofv3 --kernel-trace --stats -- python3 bench.py --workload {w} --full --no-cpu-baseline --no-batch1 --steps 20 --warmup 3"
         head = (f"# {cmd}   (MI355X, ROCm 7.2, round 3; scripts/collect_profiles.sh {w})\n"
                 f"# B = {B} instances, T = {T}; {N_STEPS} MPC steps in the run; summary of the rocpd database (scripts/rocpd_stats.py).\n"
                 "# AGX_NO_EMPTY_LAUNCHES=1 skips the trial launches of the line search when nobody searches, AGX_K1_FUSED=0 launches running and terminal nodes separately.\n")

@@ -16,7 +16,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export AGX_NO_EMPTY_LAUNCHES=1
 export AGX_K1_FUSED=0   # running / terminal nodes as separate launches: the kernel the roofline is quoted on appears alone
-ARGS="--workload $W --no-cpu-baseline --no-batch1 --steps 20 --warmup 3 $@"
+ARGS="--workload $W --full --no-cpu-baseline --no-batch1 --steps 20 --warmup 3 $@"
 rocprofv3 --kernel-trace --stats -d $OUT/trace -- python3 $ROOT/bench.py $ARGS > $OUT/trace.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -- python3 $ROOT/bench.py $ARGS > $OUT/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -- python3 $ROOT/bench.py $ARGS > $OUT/write.log 2>&1
