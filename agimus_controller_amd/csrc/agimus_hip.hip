@@ -96,6 +96,8 @@ struct agx_ocp {
   // that ran into max_solve_time would.  1.0 = wait for everyone (the default).
   double quorum_sqp = 1.0, quorum_qp = 1.0;
   bool con_lanes = true;          // constraint rows are control limits / state bounds / collision distances: k_con_eval_lj (AGX_CON_LANES=0: one lane per node)
+  bool con_wide = false;          // wide constraint set (DevCons: up to AGX_MAX_PAIRS collision pairs): k_con_eval_pairs, WIDE ADMM kernels (AGX_CON_WIDE=1 forces it where it applies)
+  int con_cs = AGX_MAX_NC;        // stride of g / y / z per node (wide sets: DevCons::cstride)
   bool admm_loop_always = false;  // AGX_ADMM_LOOP=2 (tests): k_admm_loop whatever the number of unfinished instances
   bool admm_loop = true;      // AGX_ADMM_LOOP=0: every ADMM iteration as three launches (sweep, update, reduce) instead of k_admm_loop
   int n_unfinished = 1 << 30; // instances the SQP loop still works on (host's last count): k_admm_loop serves the tail of a step, when
@@ -269,14 +271,18 @@ int user_component(int kind, int k, int nv, int nvu, bool is_ref) {
   return i < nvu ? blk * nvu + i : -1;
 }
 
+// Constraint rows a node type leaves out: inactive rows and, at the terminal node, which has no control, the residuals on u
+// (crocoddyl evaluates them with nu = 0).  The one rule of fill_cons, wide_class and fill_cons_wide.
+bool cons_row_skipped(const agx_constraint_row &c, bool terminal) {
+  return !c.active || (terminal && (c.kind == AGX_RES_CONTROL || c.kind == AGX_RES_CONTROL_GRAV));
+}
+
 int fill_cons(const agx_constraint_row *rows, int n, int nv, int nvu, const DevModel &m, DevCons &d, bool terminal) {
   std::memset(&d, 0, sizeof(d));
   int off = 0;
   for (int r = 0; r < n; ++r) {
     const agx_constraint_row &c = rows[r];
-    if (!c.active) continue;
-    // the terminal node has no control: residuals on u vanish there (crocoddyl evaluates them with nu = 0)
-    if (terminal && (c.kind == AGX_RES_CONTROL || c.kind == AGX_RES_CONTROL_GRAV)) continue;
+    if (cons_row_skipped(c, terminal)) continue;
     if (d.n >= AGX_MAX_CONS) return fail("agx_ocp_create: at most 4 active constraint rows per node type");
     if (c.kind != AGX_RES_STATE && c.kind != AGX_RES_CONTROL && !agx::cons_has_dense_rows(c.kind))
       return fail("agx_ocp_create: unknown constraint residual kind");
@@ -312,6 +318,67 @@ int fill_cons(const agx_constraint_row *rows, int n, int nv, int nvu, const DevM
     off += nr;
   }
   d.nc = off;
+  return 0;
+}
+
+// Wide constraint sets (DevCons): collision-distance rows next to at most one State and one Control row.  Class of the active rows
+// of one node type: 0 they qualify, 1 they do not (another kind, a second State / Control row), 2 more than AGX_MAX_PAIRS pairs.
+int wide_class(const agx_constraint_row *rows, int n, bool terminal) {
+  int ns = 0, nc = 0, np = 0;
+  for (int r = 0; r < n; ++r) {
+    const agx_constraint_row &c = rows[r];
+    if (cons_row_skipped(c, terminal)) continue;
+    if (c.kind == AGX_RES_STATE) ++ns;
+    else if (c.kind == AGX_RES_CONTROL) ++nc;
+    else if (c.kind == AGX_RES_COLLISION) ++np;
+    else return 1;
+  }
+  if (ns > 1 || nc > 1) return 1;
+  return np > AGX_MAX_PAIRS ? 2 : 0;
+}
+
+// The wide layout of a set wide_class accepts: State / Control rows in the row table (components first), then the pairs in the
+// caller's order at pair_off + p.  The strides are set by the caller (the same for both node types).
+int fill_cons_wide(const agx_constraint_row *rows, int n, int nv, int nvu, const DevModel &m, DevCons &d, bool terminal) {
+  std::memset(&d, 0, sizeof(d));
+  int off = 0;
+  for (int r = 0; r < n; ++r) {
+    const agx_constraint_row &c = rows[r];
+    if (cons_row_skipped(c, terminal) || c.kind == AGX_RES_COLLISION) continue;
+    // the kernels of the wide layout know State / Control rows and the pair table only (wide_class admits nothing else)
+    if ((c.kind != AGX_RES_STATE && c.kind != AGX_RES_CONTROL) || d.n >= 2)
+      return fail("agx_ocp_create: a wide constraint set holds collision pairs, at most one State and one Control row");
+    if (!c.lower || !c.upper) return fail("agx_ocp_create: constraint bounds missing");
+    const int nr = agx_row_nr(c.kind, nv), nref = agx_row_nref(c.kind, nv);
+    const int i = d.n++;
+    d.kind[i] = c.kind; d.frame[i] = c.frame; d.frame_b[i] = c.frame_b; d.off[i] = off; d.nr[i] = nr;
+    for (int k = 0; k < nref; ++k) {
+      const int ku = user_component(c.kind, k, nv, nvu, true);
+      d.ref[i][k] = (c.ref && ku >= 0) ? c.ref[ku] : 0.0;
+    }
+    for (int k = 0; k < nr; ++k) {
+      const int ku = user_component(c.kind, k, nv, nvu, false);  // pad joints: unbounded components
+      d.lb[off + k] = ku >= 0 ? c.lower[ku] : -INFINITY; d.ub[off + k] = ku >= 0 ? c.upper[ku] : INFINITY;
+      if (!(d.lb[off + k] <= d.ub[off + k])) return fail("agx_ocp_create: constraint with lower > upper");
+    }
+    off += nr;
+  }
+  d.pair_off = off;
+  for (int r = 0; r < n; ++r) {
+    const agx_constraint_row &c = rows[r];
+    if (cons_row_skipped(c, terminal) || c.kind != AGX_RES_COLLISION) continue;
+    if (d.npairs >= AGX_MAX_PAIRS) return fail("agx_ocp_create: at most " + std::to_string(AGX_MAX_PAIRS) + " collision-pair constraints per node type");
+    if (!c.lower || !c.upper) return fail("agx_ocp_create: constraint bounds missing");
+    if (c.frame < 0 || c.frame >= m.nframes || c.frame_b < 0 || c.frame_b >= m.nframes || !agx::frame_has_geometry(m, c.frame) ||
+        !agx::frame_has_geometry(m, c.frame_b))
+      return fail("agx_ocp_create: collision constraint refers to a frame without geometry");
+    if (agx::frame_is_box(m, c.frame) && agx::frame_is_box(m, c.frame_b))
+      return fail("agx_ocp_create: box / box collision pairs are not supported");
+    if (!(c.lower[0] <= c.upper[0])) return fail("agx_ocp_create: constraint with lower > upper");
+    const int p = d.npairs++;
+    d.pa[p] = c.frame; d.pb[p] = c.frame_b; d.plb[p] = c.lower[0]; d.pub[p] = c.upper[0];
+  }
+  d.nc = off + d.npairs;
   return 0;
 }
 
@@ -685,18 +752,119 @@ int quorum_count(int B, double q) {
 }
 
 // Constraint values / Jacobian rows / violation of every node at (xs, us): 8 lanes per node for serial chains whose rows are
-// control limits, state bounds and collision distances (k_con_eval_lj), else one lane per node (k_con_eval).
+// control limits, state bounds and collision distances (k_con_eval_lj, wide sets: k_con_eval_pairs), else one lane per node
+// (k_con_eval).
 template <int NV, bool CH>
 void launch_con_eval(agx_ocp *o, const double *xs, const double *us, int phase) {
   if constexpr (NV <= 7) {
     const long long nodes = (long long)o->B * (o->T + 1);
-    if (CH && o->con_lanes)
+    if (o->con_wide)
+      hipLaunchKernelGGL((agx::k_con_eval_pairs<NV>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, xs, us,
+                         o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase);
+    else if (CH && o->con_lanes)
       hipLaunchKernelGGL((agx::k_con_eval_lj<NV>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, xs, us, o->d_cg,
                          o->d_cjac, o->d_nodestat, o->d_state, phase);
     else
       hipLaunchKernelGGL((agx::k_con_eval<NV, CH>), dim3((int)((nodes + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, xs, us, o->d_cg,
                          o->d_cjac, o->d_nodestat, o->d_state, phase);
   }
+}
+
+// The ADMM loop of admm_direction for the 7-joint capacity; W: wide constraint sets (DevCons), the WIDE instances of the node kernels.
+template <int NV, bool CH, bool W>
+int admm_direction_nv7(agx_ocp *o, bool prefactor) {
+  const long long nodes = (long long)o->B * (o->T + 1);
+  const int g8 = (int)((nodes * 8 + 255) / 256), g8b = (int)((nodes * 8 + 127) / 128), g1 = (int)((nodes + 255) / 256);
+  if (prefactor) {
+    if (!o->d_Kws_lqr) {
+      HIPCHK(hipMalloc((void **)&o->d_Kws_lqr, sizeof(double) * (size_t)o->B * o->T * o->nu * o->nx));
+      HIPCHK(hipMalloc((void **)&o->d_kws_lqr, sizeof(double) * (size_t)o->B * o->T * o->nu));
+    }
+    // constraint data and the augmented Hessians need only (xs, us) and rho: before the LQR pass
+    launch_con_eval<NV, CH>(o, o->d_xs, o->d_us, 0);
+    hipLaunchKernelGGL(agx::k_admm_pre, dim3((o->B + 255) / 256), dim3(256), 0, o->stream, o->d_ocp, o->d_state);
+    hipLaunchKernelGGL((agx::k_admm_tile<NV, W>), dim3(g8b), dim3(128), 0, o->stream, o->d_ocp, o->d_qt, o->d_qt2, o->d_aux, o->d_cx,
+                       o->d_du, o->d_cjac, o->d_y, o->d_z, o->d_state, 0);  // its gradient part is rewritten below
+    hipLaunchKernelGGL((agx::k_riccati_lqr_prefactor<NV>), dim3(2 * o->B), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_qt2,
+                       o->d_aux, o->d_Kws, o->d_kws, o->d_Kws_lqr, o->d_kws_lqr, o->d_dx, o->d_w, o->d_du, o->d_Kout, o->d_state, o->d_fac);
+    if (o->admm_segments)
+      hipLaunchKernelGGL((agx::k_seg_products<NV>), dim3(o->B * agx::kSeg), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_Kws, o->d_segP,
+                         o->d_state);
+    HIPCHK(hipGetLastError());
+  }
+  if (launch_step(o, 0, 0, 0, true, false)) return -1;  // du of the initial guess (k_node_kkt)
+  HIPCHK(hipMemsetAsync(o->d_ndone + 1, 0, sizeof(int), o->stream));
+  hipLaunchKernelGGL((agx::k_admm_init<NV, W>), dim3(g1), dim3(256), 0, o->stream, o->d_ocp, o->d_dx, o->d_cx, o->d_z, o->d_state,
+                     o->d_ndone + 1);
+  if (!prefactor)
+    launch_con_eval<NV, CH>(o, o->d_xs, o->d_us, 0);
+  HIPCHK(hipGetLastError());
+  const int max_qp = o->ho.max_qp;
+  // Polls the count of converged QPs; true when the loop ends here (quorum reached: the others are capped at `iter`)
+  auto quorum_reached = [&](int iter, bool *stop) -> int {
+    int n_conv = 0;
+    *stop = false;
+    if (read_int(o, o->d_ndone + 1, 4, 5, &n_conv)) return -1;
+    if (n_conv >= quorum_count(o->B, o->quorum_qp)) {
+      if (n_conv < o->B && iter < max_qp) {  // quorum reached: the others stop here with the iterations they ran
+        hipLaunchKernelGGL(agx::k_admm_cap, dim3((o->B + 255) / 256), dim3(256), 0, o->stream, o->d_state, o->B, iter);
+        HIPCHK(hipGetLastError());
+      }
+      *stop = true;
+    }
+    return 0;
+  };
+  for (int iter = 1; iter <= max_qp;) {
+    // augmented Hessians change at the first iteration and after a rho update (k_admm_reduce decides at
+    // multiples of kRhoInterval); in between k_admm_update leaves the next gradient behind
+    const bool boundary = iter == 1 || (iter > 2 && (iter - 1) % agx::kRhoInterval == 0);
+    if (!boundary && o->admm_loop && o->admm_segments && (o->admm_loop_always || 4 * o->n_unfinished <= o->B)) {
+      // gradient-only iterations up to the next rho check in one launch per instance (k_admm_loop); with a quorum < 1 in the
+      // chunks of the host's polling schedule, so that which instances are cut does not depend on the workgroups' progress
+      int last = ((iter - 1) / agx::kRhoInterval + 1) * agx::kRhoInterval;
+      if (o->quorum_qp < 1.0) last = std::min(last, ((iter + 3) / 4) * 4);
+      last = std::min(last, max_qp);
+      hipLaunchKernelGGL((agx::k_admm_loop<NV, W>), dim3(o->B), dim3(64 * agx::kSeg), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_qt2, o->d_aux,
+                         o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_du, o->d_cx, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_nodestat,
+                         o->d_admmstat, o->d_state, o->d_fac, o->d_segP, iter, last, o->d_ndone + 1,
+                         o->general ? (const double *)o->d_auxg : (const double *)nullptr);
+      HIPCHK(hipGetLastError());
+      iter = last + 1;
+      bool stop;
+      if (quorum_reached(last, &stop)) return -1;
+      if (stop) break;
+      continue;
+    }
+    const bool pre = prefactor && iter == 1;  // Hessian and factors of this iteration exist: gradient only
+    if (boundary)
+      hipLaunchKernelGGL((agx::k_admm_tile<NV, W>), dim3(g8b), dim3(128), 0, o->stream, o->d_ocp, o->d_qt, o->d_qt2, o->d_aux, o->d_cx,
+                         o->d_du, o->d_cjac, o->d_y, o->d_z, o->d_state, pre ? 1 : 0);
+    const bool may_refactor = !pre && boundary;
+    hipLaunchKernelGGL((agx::k_riccati_admm<NV>), dim3(o->B), dim3(64 * agx::kSeg), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt2, o->d_aux,
+                       o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_du, o->d_Kout, o->d_state, o->d_fac,
+                       o->admm_segments ? (const double *)o->d_segP : (const double *)nullptr, pre ? 1 : 0);
+    if (may_refactor && o->admm_segments)  // new gains: the segments' closed-loop products for the gradient-only sweeps that follow
+      hipLaunchKernelGGL((agx::k_seg_products<NV>), dim3(o->B * agx::kSeg), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_Kws, o->d_segP,
+                         o->d_state);
+    hipLaunchKernelGGL((agx::k_admm_update<NV, W>), dim3(g8), dim3(256), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux, o->d_dx, o->d_w,
+                       o->d_du, o->d_cx, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_nodestat, o->d_admmstat, o->d_qt2, o->d_state,
+                       o->general ? (const double *)o->d_auxg : (const double *)nullptr);
+    hipLaunchKernelGGL(agx::k_admm_reduce, dim3(o->B), dim3(128), 0, o->stream, o->d_ocp, o->d_admmstat, o->d_state, iter,
+                       o->d_ndone + 1);
+    HIPCHK(hipGetLastError());
+    if (iter % 4 == 0 || iter == max_qp) {
+      bool stop;
+      if (quorum_reached(iter, &stop)) return -1;
+      if (stop) break;
+    }
+    ++iter;
+  }
+  // the gains the solver reports: those of the last ADMM backward pass, in u-space
+  const long long units = (long long)o->B * o->T * 16;
+  hipLaunchKernelGGL((agx::k_gains_to_u<NV>), dim3((int)((units + 255) / 256)), dim3(256), 0, o->stream, o->d_ocp, o->d_aux, o->d_Kws,
+                     o->d_Kout, o->d_state);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 // Constrained direction of one SQP iteration (SolverCSQP::computeDirection): the plain LQR pass has
@@ -753,98 +921,8 @@ int admm_direction(agx_ocp *o, bool prefactor = false) {
       return 0;
       }
     } else {
-    const long long nodes = (long long)o->B * (o->T + 1);
-    const int g8 = (int)((nodes * 8 + 255) / 256), g8b = (int)((nodes * 8 + 127) / 128), g1 = (int)((nodes + 255) / 256);
-    if (prefactor) {
-      if (!o->d_Kws_lqr) {
-        HIPCHK(hipMalloc((void **)&o->d_Kws_lqr, sizeof(double) * (size_t)o->B * o->T * o->nu * o->nx));
-        HIPCHK(hipMalloc((void **)&o->d_kws_lqr, sizeof(double) * (size_t)o->B * o->T * o->nu));
-      }
-      // constraint data and the augmented Hessians need only (xs, us) and rho: before the LQR pass
-      launch_con_eval<NV, CH>(o, o->d_xs, o->d_us, 0);
-      hipLaunchKernelGGL(agx::k_admm_pre, dim3((o->B + 255) / 256), dim3(256), 0, o->stream, o->d_ocp, o->d_state);
-      hipLaunchKernelGGL((agx::k_admm_tile<NV>), dim3(g8b), dim3(128), 0, o->stream, o->d_ocp, o->d_qt, o->d_qt2, o->d_aux, o->d_cx,
-                         o->d_du, o->d_cjac, o->d_y, o->d_z, o->d_state, 0);  // its gradient part is rewritten below
-      hipLaunchKernelGGL((agx::k_riccati_lqr_prefactor<NV>), dim3(2 * o->B), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_qt2,
-                         o->d_aux, o->d_Kws, o->d_kws, o->d_Kws_lqr, o->d_kws_lqr, o->d_dx, o->d_w, o->d_du, o->d_Kout, o->d_state, o->d_fac);
-      if (o->admm_segments)
-        hipLaunchKernelGGL((agx::k_seg_products<NV>), dim3(o->B * agx::kSeg), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_Kws, o->d_segP,
-                           o->d_state);
-      HIPCHK(hipGetLastError());
-    }
-    if (launch_step(o, 0, 0, 0, true, false)) return -1;  // du of the initial guess (k_node_kkt)
-    HIPCHK(hipMemsetAsync(o->d_ndone + 1, 0, sizeof(int), o->stream));
-    hipLaunchKernelGGL((agx::k_admm_init<NV>), dim3(g1), dim3(256), 0, o->stream, o->d_ocp, o->d_dx, o->d_cx, o->d_z, o->d_state,
-                       o->d_ndone + 1);
-    if (!prefactor)
-      launch_con_eval<NV, CH>(o, o->d_xs, o->d_us, 0);
-    HIPCHK(hipGetLastError());
-    const int max_qp = o->ho.max_qp;
-    // Polls the count of converged QPs; true when the loop ends here (quorum reached: the others are capped at `iter`)
-    auto quorum_reached = [&](int iter, bool *stop) -> int {
-      int n_conv = 0;
-      *stop = false;
-      if (read_int(o, o->d_ndone + 1, 4, 5, &n_conv)) return -1;
-      if (n_conv >= quorum_count(o->B, o->quorum_qp)) {
-        if (n_conv < o->B && iter < max_qp) {  // quorum reached: the others stop here with the iterations they ran
-          hipLaunchKernelGGL(agx::k_admm_cap, dim3((o->B + 255) / 256), dim3(256), 0, o->stream, o->d_state, o->B, iter);
-          HIPCHK(hipGetLastError());
-        }
-        *stop = true;
-      }
-      return 0;
-    };
-    for (int iter = 1; iter <= max_qp;) {
-      // augmented Hessians change at the first iteration and after a rho update (k_admm_reduce decides at
-      // multiples of kRhoInterval); in between k_admm_update leaves the next gradient behind
-      const bool boundary = iter == 1 || (iter > 2 && (iter - 1) % agx::kRhoInterval == 0);
-      if (!boundary && o->admm_loop && o->admm_segments && (o->admm_loop_always || 4 * o->n_unfinished <= o->B)) {
-        // gradient-only iterations up to the next rho check in one launch per instance (k_admm_loop); with a quorum < 1 in the
-        // chunks of the host's polling schedule, so that which instances are cut does not depend on the workgroups' progress
-        int last = ((iter - 1) / agx::kRhoInterval + 1) * agx::kRhoInterval;
-        if (o->quorum_qp < 1.0) last = std::min(last, ((iter + 3) / 4) * 4);
-        last = std::min(last, max_qp);
-        hipLaunchKernelGGL((agx::k_admm_loop<NV>), dim3(o->B), dim3(64 * agx::kSeg), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_qt2, o->d_aux,
-                           o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_du, o->d_cx, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_nodestat,
-                           o->d_admmstat, o->d_state, o->d_fac, o->d_segP, iter, last, o->d_ndone + 1,
-                           o->general ? (const double *)o->d_auxg : (const double *)nullptr);
-        HIPCHK(hipGetLastError());
-        iter = last + 1;
-        bool stop;
-        if (quorum_reached(last, &stop)) return -1;
-        if (stop) break;
-        continue;
-      }
-      const bool pre = prefactor && iter == 1;  // Hessian and factors of this iteration exist: gradient only
-      if (boundary)
-        hipLaunchKernelGGL((agx::k_admm_tile<NV>), dim3(g8b), dim3(128), 0, o->stream, o->d_ocp, o->d_qt, o->d_qt2, o->d_aux, o->d_cx,
-                           o->d_du, o->d_cjac, o->d_y, o->d_z, o->d_state, pre ? 1 : 0);
-      const bool may_refactor = !pre && boundary;
-      hipLaunchKernelGGL((agx::k_riccati_admm<NV>), dim3(o->B), dim3(64 * agx::kSeg), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt2, o->d_aux,
-                         o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_du, o->d_Kout, o->d_state, o->d_fac,
-                         o->admm_segments ? (const double *)o->d_segP : (const double *)nullptr, pre ? 1 : 0);
-      if (may_refactor && o->admm_segments)  // new gains: the segments' closed-loop products for the gradient-only sweeps that follow
-        hipLaunchKernelGGL((agx::k_seg_products<NV>), dim3(o->B * agx::kSeg), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_Kws, o->d_segP,
-                           o->d_state);
-      hipLaunchKernelGGL((agx::k_admm_update<NV>), dim3(g8), dim3(256), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux, o->d_dx, o->d_w,
-                         o->d_du, o->d_cx, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_nodestat, o->d_admmstat, o->d_qt2, o->d_state,
-                         o->general ? (const double *)o->d_auxg : (const double *)nullptr);
-      hipLaunchKernelGGL(agx::k_admm_reduce, dim3(o->B), dim3(128), 0, o->stream, o->d_ocp, o->d_admmstat, o->d_state, iter,
-                         o->d_ndone + 1);
-      HIPCHK(hipGetLastError());
-      if (iter % 4 == 0 || iter == max_qp) {
-        bool stop;
-        if (quorum_reached(iter, &stop)) return -1;
-        if (stop) break;
-      }
-      ++iter;
-    }
-    // the gains the solver reports: those of the last ADMM backward pass, in u-space
-    const long long units = (long long)o->B * o->T * 16;
-    hipLaunchKernelGGL((agx::k_gains_to_u<NV>), dim3((int)((units + 255) / 256)), dim3(256), 0, o->stream, o->d_ocp, o->d_aux, o->d_Kws,
-                       o->d_Kout, o->d_state);
-    HIPCHK(hipGetLastError());
-    return 0;
+      if constexpr (CH) if (o->con_wide) return admm_direction_nv7<NV, CH, true>(o, prefactor);
+      return admm_direction_nv7<NV, CH, false>(o, prefactor);
     }
   });
 }
@@ -1216,8 +1294,33 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
       }
     }
   }
-  if (fill_cons(d->running_constraints, d->n_running_constraints, o->nv, o->nvu, m->h, o->ho.cons[0], false) ||
-      fill_cons(d->terminal_constraints, d->n_terminal_constraints, o->nv, o->nvu, m->h, o->ho.cons[1], true)) { delete o; return -1; }
+  {
+    // Sets within the fixed limits keep the fixed layout; a set over them whose rows are collision pairs (at most AGX_MAX_PAIRS) with
+    // at most one State and one Control row takes the wide layout on serial chains of the 7-joint capacity; AGX_CON_WIDE=1 gives
+    // every such set the wide layout.  Everything else is refused by fill_cons.
+    const int wc_r = wide_class(d->running_constraints, d->n_running_constraints, false),
+              wc_t = wide_class(d->terminal_constraints, d->n_terminal_constraints, true);
+    const bool wide_model = o->nv <= 7 && o->chain, wide_ok = wide_model && wc_r == 0 && wc_t == 0;
+    bool wide = false;
+    if (const char *e = getenv("AGX_CON_WIDE")) wide = wide_ok && e[0] == '1';
+    if (!wide && (fill_cons(d->running_constraints, d->n_running_constraints, o->nv, o->nvu, m->h, o->ho.cons[0], false) ||
+                  fill_cons(d->terminal_constraints, d->n_terminal_constraints, o->nv, o->nvu, m->h, o->ho.cons[1], true))) {
+      if (wide_model && (wc_r == 2 || wc_t == 2)) {
+        delete o;
+        return fail("agx_ocp_create: at most " + std::to_string(AGX_MAX_PAIRS) + " collision-pair constraints per node type");
+      }
+      if (!wide_ok) { delete o; return -1; }
+      wide = true;
+    }
+    if (wide) {
+      if (fill_cons_wide(d->running_constraints, d->n_running_constraints, o->nv, o->nvu, m->h, o->ho.cons[0], false) ||
+          fill_cons_wide(d->terminal_constraints, d->n_terminal_constraints, o->nv, o->nvu, m->h, o->ho.cons[1], true)) { delete o; return -1; }
+      const int cs = std::max(1, std::max(o->ho.cons[0].nc, o->ho.cons[1].nc)), js = std::max(1, std::max(o->ho.cons[0].npairs, o->ho.cons[1].npairs));
+      for (int lay = 0; lay < 2; ++lay) { o->ho.cons[lay].cstride = cs; o->ho.cons[lay].jstride = js; }
+      o->con_wide = o->ho.cons[0].nc + o->ho.cons[1].nc > 0;
+      if (o->con_wide) o->con_cs = cs;
+    }
+  }
   for (int lay = 0; lay < 2; ++lay)
     for (int r = 0; r < o->ho.cons[lay].n; ++r) {
       const int k = o->ho.cons[lay].kind[r];
@@ -1335,10 +1438,12 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   if (o->general) ALLOC(o->d_auxg, B * (T + 1) * (size_t)(3 * o->nv * 8));
   if (o->has_con) {
     if (!o->d_qt2) ALLOC(o->d_qt2, B * (T + 1) * (size_t)o->qt_size);
-    ALLOC(o->d_cg, B * (T + 1) * AGX_MAX_NC);
-    ALLOC(o->d_cjac, B * (T + 1) * AGX_MAX_DENSE * 32);  // 24 per row up to 7 joints (q | v | u, 8 each), 32 above (q only)
-    ALLOC(o->d_y, B * (T + 1) * AGX_MAX_NC);
-    ALLOC(o->d_z, B * (T + 1) * AGX_MAX_NC);
+    const size_t cs = (size_t)o->con_cs;  // AGX_MAX_NC, wide sets: their own stride
+    ALLOC(o->d_cg, B * (T + 1) * cs);
+    if (o->con_wide) ALLOC(o->d_cjac, B * (T + 1) * (size_t)o->ho.cons[0].jstride * 8);  // distance gradients, d/dq only
+    else ALLOC(o->d_cjac, B * (T + 1) * AGX_MAX_DENSE * 32);  // 24 per row up to 7 joints (q | v | u, 8 each), 32 above (q only)
+    ALLOC(o->d_y, B * (T + 1) * cs);
+    ALLOC(o->d_z, B * (T + 1) * cs);
     ALLOC(o->d_cx, B * (T + 1) * nx);
     ALLOC(o->d_admmstat, B * (T + 1) * 4);
     ALLOC(o->d_fac, B * T * 192);
@@ -1436,7 +1541,7 @@ int agx_ocp_set_quorum(agx_ocp *o, double sqp_fraction, double qp_fraction) {
 int agx_ocp_reset_duals(agx_ocp *o) {
   if (!o) return fail("null handle");
   if (set_device(o)) return -1;
-  if (o->has_con) HIPCHK(hipMemsetAsync(o->d_y, 0, sizeof(double) * (size_t)o->B * (o->T + 1) * AGX_MAX_NC, o->stream));
+  if (o->has_con) HIPCHK(hipMemsetAsync(o->d_y, 0, sizeof(double) * (size_t)o->B * (o->T + 1) * o->con_cs, o->stream));
   hipLaunchKernelGGL(agx::k_reset_rho, dim3((o->B + 255) / 256), dim3(256), 0, o->stream, o->d_state, o->B);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(o->stream));

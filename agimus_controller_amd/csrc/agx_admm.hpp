@@ -54,7 +54,8 @@ __global__ void __launch_bounds__(64) k_con_eval(const DevModel *__restrict__ mp
 
 // Start of the ADMM loop of one SQP iteration (reset_params + equality-QP initial guess): prox centre
 // cx <- dx of the plain LQR pass (du was written by k_node_kkt), z <- 0, y kept.
-template <int NV>
+// WIDE: the wide constraint layout (DevCons: collision pairs, per-OCP stride of z); the other instances have AGX_MAX_NC.
+template <int NV, bool WIDE = false>
 __global__ void __launch_bounds__(256) k_admm_init(const DevOcp *__restrict__ op, const double *__restrict__ dxs,
                                                    double *__restrict__ cxs, double *__restrict__ zs, DevState *__restrict__ st,
                                                    int *__restrict__ n_conv) {
@@ -70,7 +71,8 @@ __global__ void __launch_bounds__(256) k_admm_init(const DevOcp *__restrict__ op
     return;
   }
   for (int i = 0; i < NX; ++i) cxs[node * NX + i] = dxs[node * NX + i];
-  for (int k = 0; k < AGX_MAX_NC; ++k) zs[node * AGX_MAX_NC + k] = 0.0;
+  const int cs = WIDE ? o.cons[0].cstride : AGX_MAX_NC;
+  for (int k = 0; k < cs; ++k) zs[node * cs + k] = 0.0;
   if (t == 0) {
     S.admm_conv = 0;
     S.admm_refactor = 1;
@@ -95,7 +97,8 @@ __global__ void k_admm_pre(const DevOcp *__restrict__ op, DevState *__restrict__
 // Augmented QP tile of one node: 8 lanes per node, lane j owns column j of every block.
 //   H  += [taux M]' diag(sigma + rho_u) [taux M] + sigma I_x + rho_x (state rows) + rho g g' (collision)
 //   g  += [taux M]' (h_u - sigma du_c) - sigma dx_c + h_x + h g,      h = y - rho z
-template <int NV>
+// WIDE: wide constraint sets (DevCons), whose collision pairs are rows on q only: a_qq += rho g g', gq += h g per pair.
+template <int NV, bool WIDE = false>
 __global__ void __launch_bounds__(128) k_admm_tile(const DevOcp *__restrict__ op, const double *__restrict__ qts,
                                                    double *__restrict__ qt2s, const double *__restrict__ auxs,
                                                    const double *__restrict__ cxs, const double *__restrict__ dus,
@@ -119,7 +122,8 @@ __global__ void __launch_bounds__(128) k_admm_tile(const DevOcp *__restrict__ op
   double *q2 = qt2s + unit * Q::SIZE;
   const double *ax = auxs + unit * A::SIZE;
   const double *cx = cxs + unit * NX;
-  const double *y = ys + unit * AGX_MAX_NC, *z = zs + unit * AGX_MAX_NC;
+  const long long cs = WIDE ? o.cons[0].cstride : AGX_MAX_NC;
+  const double *y = ys + unit * cs, *z = zs + unit * cs;
   const DevCons &c = o.cons[t == T ? 1 : 0];
   const double sig = kSigma, rs = S.rho_sparse;
   const bool jl = l8 < NV, wr = live && jl;
@@ -179,7 +183,7 @@ __global__ void __launch_bounds__(128) k_admm_tile(const DevOcp *__restrict__ op
   // on every block; the gradient terms of the u part ride in hu[] with those of the control rows
   const double *Mm = sh, *tq = sh + B2, *tv = sh + 2 * B2;
   for (int r = 0; r < c.n; ++r) {
-    if (!cons_has_dense_rows(c.kind[r])) continue;
+    if (WIDE || !cons_has_dense_rows(c.kind[r])) continue;  // (the row table of a wide set holds State / Control rows only)
     for (int e = 0; e < c.nr[r]; ++e) {
       const int off = c.off[r] + e;
       const double *gj = cjac + (unit * AGX_MAX_DENSE + c.coll_slot[r] + e) * 24;
@@ -209,6 +213,20 @@ __global__ void __launch_bounds__(128) k_admm_tile(const DevOcp *__restrict__ op
             a_vw[i] += rho * cvi * cw;
           }
         }
+      }
+    }
+  }
+  if constexpr (WIDE) {  // collision pairs [B][T+1][jstride][8]: no v / u part, so only the qq block and the q gradient change
+    for (int p = 0; p < c.npairs; ++p) {
+      const int off = c.pair_off + p;
+      const double *gp = cjac + (unit * c.jstride + p) * 8;
+      const double rho = admm_rho(c.plb[p], c.pub[p], rs);
+      const double h = y[off] - rho * z[off];
+      const double cq = gp[j];
+      gq += h * cq;
+      if (full) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) a_qq[i] += rho * gp[i] * cq;
       }
     }
   }
@@ -671,7 +689,8 @@ __global__ void __launch_bounds__(64, 2) k_riccati_lqr_prefactor(const DevOcp *_
 //   Lx + Fx' lam' - lam + Gx' y = -[(Lxx + dreg) dx + sigma (dx - dx_c) + Gx' (rho C d + h - y)],  h = y_old - rho z_old
 // (device function: called by k_admm_update for the whole batch and by k_admm_loop for the nodes of its instance; out4: the
 // node's primal / dual residual norms and their scales, zero for lanes without a node)
-template <int NV>
+// WIDE: wide constraint sets (DevCons): the collision pairs after the State / Control rows, Jacobian rows on q only.
+template <int NV, bool WIDE = false>
 __device__ __forceinline__ void admm_update_node(const DevOcp *op, const long long node, const bool ok_in, const double *qts,
                                                  const double *auxs, const double *dxs, const double *wss, double *dus,
                                                  double *cxs, const double *cg, const double *cjac, double *ys, double *zs,
@@ -699,8 +718,9 @@ __device__ __forceinline__ void admm_update_node(const DevOcp *op, const long lo
   const double *ax = auxs + nid * A::SIZE;
   const double *dx = dxs + nid * NX;
   double *cx = cxs + nid * NX;
-  double *y = ys + nid * AGX_MAX_NC, *z = zs + nid * AGX_MAX_NC;
-  const double *g = cg + nid * AGX_MAX_NC;
+  const long long cs = WIDE ? o.cons[0].cstride : AGX_MAX_NC;
+  double *y = ys + nid * cs, *z = zs + nid * cs;
+  const double *g = cg + nid * cs;
   const DevCons &c = o.cons[t == T ? 1 : 0];
   const double dq = jl ? dx[jj] : 0.0, dv = jl ? dx[NV + jj] : 0.0;
   const double cq = jl ? cx[jj] : 0.0, cv = jl ? cx[NV + jj] : 0.0;
@@ -727,12 +747,12 @@ __device__ __forceinline__ void admm_update_node(const DevOcp *op, const long lo
   double dual_q = 0.0, dual_v = 0.0, dual_u = 0.0, drel_q = 0.0, drel_v = 0.0, drel_u = 0.0;  // (G' rho dz)_j, (G' y)_j
   double e_q = 0.0, e_v = 0.0, e_u = 0.0;                                                   // (G' (rho C d + h - y))_j
   double hn_q = 0.0, hn_v = 0.0, hn_u = 0.0;  // (G' (y - rho z))_j with the updated y, z: the next iteration's gradient terms
-  auto comp = [&](int k, double Cd, double &dual, double &drel, double &e, double jac) {
-    const double rho = admm_rho(c.lb[k], c.ub[k], rs);
+  auto comp_lu = [&](int k, double lb, double ub, double Cd, double &dual, double &drel, double &e, double jac) {
+    const double rho = admm_rho(lb, ub, rs);
     const double z0 = z[k], y0 = y[k];
     const double zrel = kAlphaRelax * Cd + (1.0 - kAlphaRelax) * z0;
     double zn = zrel + y0 / rho;
-    zn = fmin(fmax(zn, c.lb[k] - g[k]), c.ub[k] - g[k]);
+    zn = fmin(fmax(zn, lb - g[k]), ub - g[k]);
     const double yn = y0 + rho * (zrel - zn);
     primal = fmax(primal, fabs(Cd - zn));
     primal_rel = fmax(primal_rel, fmax(fabs(Cd), fabs(zn)));
@@ -740,6 +760,9 @@ __device__ __forceinline__ void admm_update_node(const DevOcp *op, const long lo
     drel += jac * yn;
     e += jac * (rho * Cd + (y0 - rho * z0) - yn);
     return (double2){zn, yn};
+  };
+  auto comp = [&](int k, double Cd, double &dual, double &drel, double &e, double jac) {
+    return comp_lu(k, c.lb[k], c.ub[k], Cd, dual, drel, e, jac);
   };
   for (int r = 0; r < c.n; ++r) {
     const int off = c.off[r];
@@ -757,7 +780,7 @@ __device__ __forceinline__ void admm_update_node(const DevOcp *op, const long lo
         hn_v += bq.y - admm_rho(c.lb[off + NV + jj], c.ub[off + NV + jj], rs) * bq.x;
         if (act) { z[off + jj] = a.x; y[off + jj] = a.y; z[off + NV + jj] = bq.x; y[off + NV + jj] = bq.y; }
       }
-    } else if (cons_has_dense_rows(c.kind[r])) {
+    } else if (!WIDE && cons_has_dense_rows(c.kind[r])) {  // (the row table of a wide set holds State / Control rows only)
       for (int e = 0; e < c.nr[r]; ++e) {
         const double *row = cjac + (nid * AGX_MAX_DENSE + c.coll_slot[r] + e) * 24;
         const double gqj = jl ? row[jj] : 0.0, gvj = jl ? row[8 + jj] : 0.0, guj = (jl && t < T) ? row[16 + jj] : 0.0;
@@ -773,6 +796,17 @@ __device__ __forceinline__ void admm_update_node(const DevOcp *op, const long lo
         hn_q += hn * gqj; hn_v += hn * gvj; hn_u += hn * guj;
         if (act && l8 == 0) { z[off + e] = zy.x; y[off + e] = zy.y; }
       }
+    }
+  }
+  if constexpr (WIDE) {  // collision pairs: the dense-row update above with Gv = Gu = 0
+    for (int p = 0; p < c.npairs; ++p) {
+      const int k = c.pair_off + p;
+      const double gqj = jl ? cjac[(nid * c.jstride + p) * 8 + jj] : 0.0;
+      double Cd = gqj * dq;
+      Cd += dpp_xor4(Cd); Cd += dpp_xor2(Cd); Cd += dpp_xor1(Cd);
+      const double2 zy = comp_lu(k, c.plb[p], c.pub[p], Cd, dual_q, drel_q, e_q, gqj);
+      hn_q += (zy.y - admm_rho(c.plb[p], c.pub[p], rs) * zy.x) * gqj;
+      if (act && l8 == 0) { z[k] = zy.x; y[k] = zy.y; }
     }
   }
   // general cost rows (ControlGrav / FrameVelocity, agx_general.hpp): the blocks Lqv | Lvvd | Lqu of the node's Hessian in the
@@ -841,7 +875,7 @@ __device__ __forceinline__ void admm_update_node(const DevOcp *op, const long lo
   }
 }
 
-template <int NV>
+template <int NV, bool WIDE = false>
 __global__ void __launch_bounds__(256) k_admm_update(const DevOcp *__restrict__ op, const double *__restrict__ qts,
                                                      const double *__restrict__ auxs, const double *__restrict__ dxs,
                                                      const double *__restrict__ wss, double *__restrict__ dus,
@@ -851,7 +885,7 @@ __global__ void __launch_bounds__(256) k_admm_update(const DevOcp *__restrict__ 
                                                      double *__restrict__ admmstat, double *__restrict__ qt2s,
                                                      const DevState *__restrict__ st, const double *__restrict__ auxg) {
   double out4[4];
-  admm_update_node<NV>(op, ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 3, true, qts, auxs, dxs, wss, dus, cxs, cg, cjac, ys, zs,
+  admm_update_node<NV, WIDE>(op, ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 3, true, qts, auxs, dxs, wss, dus, cxs, cg, cjac, ys, zs,
                        nodestat, admmstat, qt2s, st, out4, auxg);
 }
 
@@ -913,7 +947,7 @@ __global__ void __launch_bounds__(128) k_admm_reduce(const DevOcp *__restrict__ 
 // the CU.  Three dependent launches per iteration (4.5 us each from dispatch to completion) and the host's poll every
 // four iterations go away; an instance leaves the loop at its own convergence.  Quorum < 1 keeps the host's schedule
 // (chunks of four iterations: which instances are cut must not depend on how the workgroups happen to progress).
-template <int NV>
+template <int NV, bool WIDE = false>
 __global__ void __launch_bounds__(64 * kSeg) k_admm_loop(const DevOcp *op, const double *dts, const double *qts, double *qt2s,
                                                          const double *auxs, const double *Kws, double *kws, double *dxs,
                                                          double *wss, double *dus, double *cxs, const double *cg,
@@ -934,7 +968,7 @@ __global__ void __launch_bounds__(64 * kSeg) k_admm_loop(const DevOcp *op, const
     for (int base = 0; base <= T; base += 8 * kSeg) {
       const int t = base + (tid >> 3);
       double out4[4];
-      admm_update_node<NV>(op, (long long)b * (T + 1) + (t <= T ? t : T), t <= T, qts, auxs, dxs, wss, dus, cxs, cg, cjac, ys, zs, nodestat,
+      admm_update_node<NV, WIDE>(op, (long long)b * (T + 1) + (t <= T ? t : T), t <= T, qts, auxs, dxs, wss, dus, cxs, cg, cjac, ys, zs, nodestat,
                            admmstat, qt2s, st, out4, auxg);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = fmax(v[k], out4[k]);

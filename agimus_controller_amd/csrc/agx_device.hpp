@@ -65,12 +65,23 @@ struct DevRows {
 #else
 #define AGX_MAX_NC 104
 #endif
+// Wide constraint sets (7-joint capacity, serial chains): up to AGX_MAX_PAIRS collision-distance rows next to at most one State
+// and one Control row.  The State / Control rows stay in the row table above (n <= 2, ncoll = 0); the pairs live in a table of
+// their own, component pair_off + p of the node's constraint vector.  g / y / z are [B][T+1][cstride], the distance gradients
+// [B][T+1][jstride][8] (d/dq only: a distance depends on q alone).  Kernels: k_con_eval_pairs, the WIDE instances of the ADMM
+// node kernels (agx_admm.hpp).
+#define AGX_MAX_PAIRS 64
 struct DevCons {
   int n, nc, ncoll, pad;  // rows, components, Jacobian slots in use (ncoll: historically the collision rows)
   int kind[AGX_MAX_CONS], frame[AGX_MAX_CONS], frame_b[AGX_MAX_CONS], off[AGX_MAX_CONS], nr[AGX_MAX_CONS];
   int coll_slot[AGX_MAX_CONS];  // first Jacobian slot (of AGX_MAX_DENSE) of a row whose components have dense gradients in q
   double ref[AGX_MAX_CONS][2 * AGX_MAX_NV];
   double lb[AGX_MAX_NC], ub[AGX_MAX_NC];
+  // wide sets only (zero otherwise)
+  int npairs, pair_off;    // collision pairs of this node type, component of pair 0
+  int cstride, jstride;    // per-OCP strides of g / y / z and of the distance gradients (the same in both node types)
+  int pa[AGX_MAX_PAIRS], pb[AGX_MAX_PAIRS];           // frames of pair p
+  double plb[AGX_MAX_PAIRS], pub[AGX_MAX_PAIRS];      // bounds of pair p
 };
 
 struct DevOcp {

@@ -848,4 +848,156 @@ __global__ void __launch_bounds__(64) k_con_eval_lj(const DevModel *__restrict__
   if (act && l8 == 0) nodestat[node * 4 + 3] = v;
 }
 
+// Constraint values, distance gradients and the l1 violation of every node for the WIDE constraint sets (DevCons: up to
+// AGX_MAX_PAIRS collision pairs next to at most one State and one Control row).  8 lanes per node as k_con_eval_lj: lane j forms
+// the world placement of joint j (SE3 prefix product) and stages it in LDS with the joint's world axis; the pairs are dealt
+// round-robin over the 8 lanes of the node (lane l: pairs l, l + 8, ...), and each lane evaluates the closest points of its pairs
+// and their whole gradient row in q from the staged joints (serial chain: joints up to a frame's parent move it; a self-collision
+// pair gets the terms of both frames).  State / Control rows as in k_con_eval_lj.
+// cg [B][T+1][cstride], cjac [B][T+1][jstride][8] (d/dq: a distance depends on q alone).
+template <int NV>
+__global__ void __launch_bounds__(64) k_con_eval_pairs(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
+                                                       const double *__restrict__ xs, const double *__restrict__ us,
+                                                       double *__restrict__ cg, double *__restrict__ cjac,
+                                                       double *__restrict__ nodestat, const DevState *__restrict__ st, int phase) {
+  constexpr int NX = 2 * NV;
+  __shared__ double s_mod[8][16];     // placement 12 | axis 3 of every joint
+  __shared__ double s_kin[8][8][16];  // [node of the block][joint]: world rotation 9 | origin 3 | axis 3
+  const DevModel &m = *mp;
+  const DevOcp &o = *op;
+  const int T = o.T, l8 = threadIdx.x & 7, grp = threadIdx.x >> 3;
+  const long long cs = o.cons[0].cstride, js = o.cons[0].jstride;
+  const long long n_nodes = (long long)o.B * (T + 1);
+  const long long node_raw = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 3;
+  const bool ok = node_raw < n_nodes;
+  const long long node = ok ? node_raw : n_nodes - 1;
+  const int b = (int)(node / (T + 1)), t = (int)(node % (T + 1));
+  const bool act = ok && k1_active(st[b], phase);
+  if (!__any(act)) return;
+  if (threadIdx.x < 8) {
+    const int jj = threadIdx.x < NV ? threadIdx.x : NV - 1;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) s_mod[threadIdx.x][e] = m.placement[jj][e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) s_mod[threadIdx.x][12 + e] = m.axis[jj][e];
+  }
+  __syncthreads();
+  const DevCons &c = o.cons[t == T ? 1 : 0];
+  const bool jl = l8 < NV;
+  const int j = jl ? l8 : NV - 1;
+  const double *xp = xs + node * NX;
+  const double qj = xp[j], vj = xp[NV + j];
+  const double uj = (t < T) ? us[((long long)b * T + t) * NV + j] : 0.0;
+  double *kin = s_kin[grp][l8];
+  if (c.npairs > 0) {  // kinematics of k_con_eval_lj, staged for the lanes of the node
+    const double *mj = s_mod[l8];
+    const double *ax3 = mj + 12;
+    double R[9], p[3], z[3];
+    double sn, cs_;
+    sincos(qj, &sn, &cs_);
+    const double omc = 1.0 - cs_;
+    double Rq[9];
+    Rq[0] = cs_ + omc * ax3[0] * ax3[0];
+    Rq[1] = omc * ax3[0] * ax3[1] - sn * ax3[2];
+    Rq[2] = omc * ax3[0] * ax3[2] + sn * ax3[1];
+    Rq[3] = omc * ax3[1] * ax3[0] + sn * ax3[2];
+    Rq[4] = cs_ + omc * ax3[1] * ax3[1];
+    Rq[5] = omc * ax3[1] * ax3[2] - sn * ax3[0];
+    Rq[6] = omc * ax3[2] * ax3[0] - sn * ax3[1];
+    Rq[7] = omc * ax3[2] * ax3[1] + sn * ax3[0];
+    Rq[8] = cs_ + omc * ax3[2] * ax3[2];
+    mm3(mj, Rq, R);
+    p[0] = mj[9]; p[1] = mj[10]; p[2] = mj[11];
+    auto se3_step = [&](auto OFFc) {
+      constexpr int OFF = decltype(OFFc)::value;
+      double Rp[9], pp[3];
+#pragma unroll
+      for (int e = 0; e < 9; ++e) Rp[e] = g_up<OFF>(R[e]);
+#pragma unroll
+      for (int e = 0; e < 3; ++e) pp[e] = g_up<OFF>(p[e]);
+      if (l8 >= OFF) {
+        double tt[3];
+        mv3(Rp, p, tt);
+        p[0] = pp[0] + tt[0]; p[1] = pp[1] + tt[1]; p[2] = pp[2] + tt[2];
+        mm3(Rp, R, R);
+      }
+    };
+    se3_step(std::integral_constant<int, 1>());
+    se3_step(std::integral_constant<int, 2>());
+    se3_step(std::integral_constant<int, 4>());
+    mv3(R, ax3, z);  // joint axis in the world
+#pragma unroll
+    for (int e = 0; e < 9; ++e) kin[e] = R[e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) { kin[9 + e] = p[e]; kin[12 + e] = z[e]; }
+  }
+  wave_lds_sync();  // the block is one wave: the joints of every node are staged
+  double v = 0.0;
+  for (int r = 0; r < c.n; ++r) {  // State / Control rows (the host puts nothing else in the row table of a wide set)
+    const int kind = c.kind[r], off = c.off[r];
+    if (kind == AGX_RES_CONTROL) {
+      const double g = uj - c.ref[r][j];
+      if (jl) {
+        if (act) cg[node * cs + off + j] = g;
+        v += fmax(c.lb[off + j] - g, 0.0) + fmax(g - c.ub[off + j], 0.0);
+      }
+    } else if (kind == AGX_RES_STATE) {
+      const double gq = qj - c.ref[r][j], gv = vj - c.ref[r][NV + j];
+      if (jl) {
+        if (act) { cg[node * cs + off + j] = gq; cg[node * cs + off + NV + j] = gv; }
+        v += fmax(c.lb[off + j] - gq, 0.0) + fmax(gq - c.ub[off + j], 0.0) + fmax(c.lb[off + NV + j] - gv, 0.0) + fmax(gv - c.ub[off + NV + j], 0.0);
+      }
+    }
+  }
+  const double(*sk)[16] = s_kin[grp];
+  for (int pi = l8; pi < c.npairs; pi += 8) {
+    const int fr[2] = {c.pa[pi], c.pb[pi]};
+    double Rg[2][9], pg[2][3];
+    int jp[2];
+#pragma unroll
+    for (int gi = 0; gi < 2; ++gi) {
+      const double *fpl = m.frame_placement[fr[gi]];
+      const int jf = m.frame_parent[fr[gi]];
+      jp[gi] = jf;
+      if (jf >= 0) {
+        const double *Rp = sk[jf], *pp = sk[jf] + 9;
+        double tt[3];
+        mm3(Rp, fpl, Rg[gi]);
+        mv3(Rp, fpl + 9, tt);
+        pg[gi][0] = pp[0] + tt[0]; pg[gi][1] = pp[1] + tt[1]; pg[gi][2] = pp[2] + tt[2];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) Rg[gi][e] = fpl[e];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) pg[gi][e] = fpl[9 + e];
+      }
+    }
+    double ca[3], cb[3], nn[3];
+    const double d = collision_distance_placed(m, fr[0], fr[1], Rg[0], pg[0], Rg[1], pg[1], ca, cb, nn);
+    double grow[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      grow[i] = 0.0;
+      if (i < NV) {
+        const double *pj = sk[i] + 9, *zj = sk[i] + 12;
+        double da[3], db[3], ta[3], tb[3];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) { da[e] = ca[e] - pj[e]; db[e] = cb[e] - pj[e]; }
+        cross3(zj, da, ta);
+        cross3(zj, db, tb);
+        grow[i] = (i <= jp[0] ? dot3(nn, ta) : 0.0) - (i <= jp[1] ? dot3(nn, tb) : 0.0);
+      }
+    }
+    if (act) {
+      double2 *row = reinterpret_cast<double2 *>(cjac + (node * js + pi) * 8);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) row[i] = make_double2(grow[2 * i], grow[2 * i + 1]);
+      cg[node * cs + c.pair_off + pi] = d;
+    }
+    v += fmax(c.plb[pi] - d, 0.0) + fmax(d - c.pub[pi], 0.0);
+  }
+  v += dpp_xor4(v); v += dpp_xor2(v); v += dpp_xor1(v);
+  if (act && l8 == 0) nodestat[node * 4 + 3] = v;
+}
+
 }  // namespace agx

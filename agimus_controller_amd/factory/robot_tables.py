@@ -227,17 +227,25 @@ PANDA_CAPSULES = {
 
 
 def panda_collision_table(armature=0.1, obstacle_xyz=(1.535, 0.0, 0.43), obstacle_radius=0.1, obstacle_length=0.4,
-                          obstacle_box=None) -> RobotTable:
+                          obstacle_box=None, obstacles=()) -> RobotTable:
     """panda_table plus link capsules and the capsule obstacle `obstacle` of the reference's
     tests/resources/environment.xacro:23-24 (xyz 1.535 0 0.43, direction x, radius 0.1, length 0.4).
-    obstacle_box = (hx, hy, hz): a box obstacle of those half extents instead (world axes)."""
+    obstacle_box = (hx, hy, hz): a box obstacle of those half extents instead (world axes).
+    obstacles: further world-fixed geometries after `obstacle`, each a dict with `name`, `xyz` and either `radius` (+ `halflen`:
+    a capsule along world x, 0 or absent: a sphere) or `box` (half extents, world axes)."""
     t = panda_table(armature)
     for name, (parent, placement, radius, halflen) in PANDA_CAPSULES.items():
         t = t.with_geometry(name, parent, placement, radius, halflen)
     if obstacle_box is not None:
-        return t.with_geometry("obstacle", -1, se3(None, list(obstacle_xyz)), box=obstacle_box)
-    # capsule axis (local z) along world x
-    return t.with_geometry("obstacle", -1, se3(_ry(np.pi / 2), list(obstacle_xyz)), obstacle_radius, obstacle_length / 2)
+        t = t.with_geometry("obstacle", -1, se3(None, list(obstacle_xyz)), box=obstacle_box)
+    else:  # capsule axis (local z) along world x
+        t = t.with_geometry("obstacle", -1, se3(_ry(np.pi / 2), list(obstacle_xyz)), obstacle_radius, obstacle_length / 2)
+    for ob in obstacles:
+        if ob.get("box") is not None:
+            t = t.with_geometry(ob["name"], -1, se3(None, list(ob["xyz"])), box=ob["box"])
+        else:
+            t = t.with_geometry(ob["name"], -1, se3(_ry(np.pi / 2), list(ob["xyz"])), ob["radius"], ob.get("halflen", 0.0))
+    return t
 
 
 def _random_body(rng, mass_range=(0.5, 4.0), size=0.15):

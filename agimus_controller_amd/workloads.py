@@ -48,6 +48,41 @@ def collision_avoidance_rows(table, frame: int, pair=("panda_link7_capsule_0", "
     return running + [_abi.RowSpec(_abi.RES_COLLISION, **dist)], terminal + [_abi.RowSpec(_abi.RES_COLLISION, **dist)]
 
 
+def collision_pair_constraints(table, pairs, lower, upper=np.inf):
+    """Constraint rows lower <= distance(a, b) <= upper of the ConstraintModelResidual items on ResidualDistanceCollision
+    (ocp_croco_generic.py:594-640 upstream), one per geometry pair (a, b) of `pairs` (frame names or ids).  lower / upper: one
+    value for every pair or one per pair.  Up to 64 pairs per node type run on the device (wide constraint sets)."""
+    pairs = list(pairs)
+    lo = np.broadcast_to(np.asarray(lower, dtype=float), (len(pairs),))
+    up = np.broadcast_to(np.asarray(upper, dtype=float), (len(pairs),))
+    fid = lambda f: f if isinstance(f, (int, np.integer)) else table.frame_id(f)  # noqa: E731
+    return [_abi.ConstraintSpec(_abi.RES_COLLISION, lower=float(lo[i]), upper=float(up[i]), frame=int(fid(a)), frame_b=int(fid(b)),
+                                name=f"collision_{i}") for i, (a, b) in enumerate(pairs)]
+
+
+# link capsules of robot_tables.panda_collision_table and four pairs of them that do not touch in normal postures
+PANDA_LINK_CAPSULES = ["panda_link2_capsule_0", "panda_link3_capsule_0", "panda_link4_capsule_0", "panda_link5_capsule_0",
+                       "panda_link7_capsule_0"]
+PANDA_SELF_COLLISION_PAIRS = [("panda_link2_capsule_0", "panda_link7_capsule_0"), ("panda_link3_capsule_0", "panda_link7_capsule_0"),
+                              ("panda_link2_capsule_0", "panda_link5_capsule_0"), ("panda_link2_capsule_0", "panda_link4_capsule_0")]
+
+
+def random_obstacles(n: int, seed: int = 11):
+    """n seeded world-fixed obstacles ob0, ob1, ... in front of the Panda (capsules along world x, spheres and boxes in turn), in
+    the form of panda_collision_table(obstacles=...)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        xyz = (rng.uniform(0.25, 0.65), rng.uniform(-0.35, 0.35), rng.uniform(0.15, 0.75))
+        if i % 3 == 0:
+            out.append(dict(name=f"ob{i}", xyz=xyz, radius=rng.uniform(0.03, 0.07), halflen=rng.uniform(0.05, 0.15)))
+        elif i % 3 == 1:
+            out.append(dict(name=f"ob{i}", xyz=xyz, radius=rng.uniform(0.03, 0.07)))
+        else:
+            out.append(dict(name=f"ob{i}", xyz=xyz, box=tuple(rng.uniform(0.03, 0.06, 3))))
+    return out
+
+
 def golden_problem():
     """The reference's only golden case, agimus_controller/tests/test_ocp_croco_base.py:14-155:
     Panda, T = 9, Euler step 1e-3, stateReg 0.1 / ctrlReg 1e-4 / placement 1.0 to (1,1,1),
