@@ -81,10 +81,7 @@ struct agx_ocp {
   bool lanes_coll = false;  // ... in its variant with one collision cost row
   bool speculate = true;  // AGX_SPECULATE_GAINS=0: gains sweep only on exit
   bool gains_mfma = true; // AGX_GAINS_MFMA=0: scalar K = M Kw - taux for large models
-  bool fuse_kkt = false;     // AGX_FUSED_KKT=1: K3 inside the forward pass of k_riccati_mx instead of its own launch (measured: no gain)
   bool riccati_mx = true;    // AGX_RICCATI_MX=0: nv <= 7 sweeps on the 8 x 8 lane grid (k_riccati) instead of the MFMA operand layout (k_riccati_mx)
-  bool riccati_mfma = true;  // AGX_RICCATI_MFMA=0: large models sweep with the LDS Gauss-Jordan kernel (k_riccati_big)
-  bool riccati_blk = true;   // AGX_RICCATI_BLK=0: the matrix-core sweep with the per-wave v_readlane elimination (k_riccati_mfma) instead of the blocked inverse (k_riccati_blk)
   // Exact two-level sweep (agx_riccati_mx2.hpp): the horizon in mx2_S segments swept in parallel; 0 = the one-wave sweep.
   // Chosen from the batch at creation (small batches leave most of the chip idle), AGX_MX2_SEGMENTS=n overrides (0: off).
   int mx2_S = 0;
@@ -412,7 +409,9 @@ int dispatch(int nv, bool chain, F &&f) {
     AGX_FOR_NV(AGX_CASE)
 #undef AGX_CASE
   }
-  return fail("no kernel instantiation for nv = " + std::to_string(nv) + " (compiled capacities: 7, 30, 32)");
+#define AGX_NAME(N) " " #N
+  return fail("no kernel instantiation for nv = " + std::to_string(nv) + " (compiled capacities:" AGX_FOR_NV(AGX_NAME) ")");
+#undef AGX_NAME
 }
 
 int ensure_canonical_tiles(agx_ocp *o) {
@@ -510,10 +509,12 @@ int launch_calc_qp(agx_ocp *o, bool running_only = false, bool term_only = false
   });
 }
 
-// K3 (k_node_kkt) folded into the forward pass of K2 (AGX_FUSED_KKT=1; off by default: the 12-value prefetch sets of
-// that pass end up behind register copies on the loop latch and the pass gains 65 us for the 51 us K3 takes alone):
-// the MFMA-layout sweep of unconstrained problems without general cost rows (those have their own node kernels).
-static inline bool fused_kkt(const agx_ocp *o) { return o->fuse_kkt && o->riccati_mx && o->nv <= 7 && !o->has_con && !o->general; }
+// K2 of large models on `tiles` (k_riccati_blk, agx_big_k2.hpp, which documents forward / gains_pass)
+template <int NV>
+void launch_riccati_blk(agx_ocp *o, const double *tiles, int forward, int gains_pass) {
+  hipLaunchKernelGGL((agx::k_riccati_blk<NV>), dim3(o->B), dim3(256), 0, o->stream, o->d_ocp, o->d_dt, tiles, o->d_Kws, o->d_kws, o->d_dx,
+                     o->d_w, o->d_state, forward, gains_pass);
+}
 
 // K2: direction sweep; with `pair` the speculative gains sweep of SQP iteration `iter` rides in the same launch
 int launch_riccati(agx_ocp *o, int forward, bool pair = false, int iter = 0, const double *tiles = nullptr) {
@@ -540,35 +541,21 @@ int launch_riccati(agx_ocp *o, int forward, bool pair = false, int iter = 0, con
       return 0;
     }
     if constexpr (NV <= 7) {
-      const int fwd = forward ? (fused_kkt(o) ? 2 : 1) : 0;  // 2: K3 rides along in the forward pass
       if (pair && o->riccati_mx)
         hipLaunchKernelGGL((agx::k_riccati_mx_pair<NV>), dim3(16 * ((o->B + 7) / 8)), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_aux,
-                           o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_Kout, o->d_state, iter, fused_kkt(o) ? 2 : 1, o->d_du, o->d_nodestat);
+                           o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_Kout, o->d_state, iter);
       else if (pair)
         hipLaunchKernelGGL((agx::k_riccati_pair<NV>), dim3(2 * o->B), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_aux,
                            o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_du, o->d_Kout, o->d_state, iter);
       else if (o->riccati_mx)
         hipLaunchKernelGGL((agx::k_riccati_mx<NV, false>), dim3(o->B), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, qt, o->d_aux,
-                           o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_Kout, o->d_state, fwd, 0, o->d_du, o->d_nodestat);
+                           o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_Kout, o->d_state, forward, 0);
       else
         hipLaunchKernelGGL((agx::k_riccati<NV, false>), dim3(o->B), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, qt, o->d_aux,
                            o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_du, o->d_Kout, o->d_state, forward, 0);
     } else {
       (void)pair; (void)iter;
-      if constexpr (NV >= 16) if (o->riccati_mfma) {
-        bool blk = o->riccati_blk;
-        if constexpr (NV == 16) blk = true;  // k_riccati_mfma tiles 16 < nv <= 32 only
-        if (blk)
-          hipLaunchKernelGGL((agx::k_riccati_blk<NV>), dim3(o->B), dim3(256), 0, o->stream, o->d_ocp, o->d_dt, qt, o->d_Kws, o->d_kws, o->d_dx,
-                             o->d_w, o->d_state, forward, 0);
-        if constexpr (NV > 16) if (!blk)
-          hipLaunchKernelGGL((agx::k_riccati_mfma<NV>), dim3(o->B), dim3(256), 0, o->stream, o->d_ocp, o->d_dt, qt, o->d_Kws, o->d_kws, o->d_dx,
-                             o->d_w, o->d_state, forward, 0);
-        HIPCHK(hipGetLastError());
-        return 0;
-      }
-      hipLaunchKernelGGL((agx::k_riccati_big<NV>), dim3(o->B), dim3(256), 0, o->stream, o->d_ocp, o->d_dt, qt, o->d_Kws, o->d_kws, o->d_dx,
-                         o->d_w, o->d_state, forward, 0);
+      launch_riccati_blk<NV>(o, qt, forward, 0);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -606,7 +593,7 @@ int launch_step(agx_ocp *o, int iter, int max_iter, int mode, bool with_node_kkt
       HIPCHK(hipGetLastError());
       return 0;
     }
-    if (with_node_kkt && !fused_kkt(o)) {
+    if (with_node_kkt) {
       if constexpr (NV <= 7)
         hipLaunchKernelGGL((agx::k_node_kkt<NV>), dim3((int)((nodes * 8 + 255) / 256)), dim3(256), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
                            o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
@@ -632,7 +619,7 @@ int launch_gains(agx_ocp *o, int gmode = 0) {
     if constexpr (NV <= 7) {
       if (o->riccati_mx)
         hipLaunchKernelGGL((agx::k_riccati_mx<NV, true>), dim3(o->B), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_aux, o->d_Kws,
-                           o->d_kws, o->d_dx, o->d_w, o->d_Kout, o->d_state, 0, gmode, (double *)nullptr, (double *)nullptr);
+                           o->d_kws, o->d_dx, o->d_w, o->d_Kout, o->d_state, 0, gmode);
       else
       hipLaunchKernelGGL((agx::k_riccati<NV, true>), dim3(o->B), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_aux, o->d_Kws,
                          o->d_kws, o->d_dx, o->d_w, o->d_du, o->d_Kout, o->d_state, 0, gmode);
@@ -642,21 +629,7 @@ int launch_gains(agx_ocp *o, int gmode = 0) {
       const long long nodes = (long long)o->B * (o->T + 1);
       const int gsel = gmode == 0 ? 1 : gmode;
       hipLaunchKernelGGL((agx::k_sigma_tile_big<NV>), dim3((int)nodes), dim3(256), 0, o->stream, o->d_ocp, o->d_qt, o->d_qt2, o->d_aux);
-      bool swept = false;
-      if constexpr (NV >= 16) if (o->riccati_mfma) {
-        bool blk = o->riccati_blk;
-        if constexpr (NV == 16) blk = true;
-        if (blk)
-          hipLaunchKernelGGL((agx::k_riccati_blk<NV>), dim3(o->B), dim3(256), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt2, o->d_Kws, o->d_kws,
-                             o->d_dx, o->d_w, o->d_state, 0, gsel);
-        if constexpr (NV > 16) if (!blk)
-          hipLaunchKernelGGL((agx::k_riccati_mfma<NV>), dim3(o->B), dim3(256), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt2, o->d_Kws, o->d_kws,
-                             o->d_dx, o->d_w, o->d_state, 0, gsel);
-        swept = true;
-      }
-      if (!swept)
-      hipLaunchKernelGGL((agx::k_riccati_big<NV>), dim3(o->B), dim3(256), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt2, o->d_Kws, o->d_kws,
-                         o->d_dx, o->d_w, o->d_state, 0, gsel);
+      launch_riccati_blk<NV>(o, o->d_qt2, 0, gsel);
       if constexpr (NV > 16) {
         if (o->gains_mfma) {  // the dense feedback-gain GEMM on the matrix cores
           hipLaunchKernelGGL((agx::k_gains_to_u_mfma<NV>), dim3(o->B * o->T), dim3(64), 0, o->stream, o->d_ocp, o->d_aux, o->d_Kws, o->d_Kout,
@@ -880,8 +853,6 @@ int admm_direction(agx_ocp *o, bool prefactor = false) {
       // augmented tile); the node kernels are k_admm_tile_big / k_admm_update_big (agx_big.hpp), norms and rho schedule
       // as for the 7-joint path (k_admm_reduce).
       (void)CH; (void)prefactor;
-      if constexpr (NV < 16) return fail("constraints for large models need the blocked sweep (capacity >= 16)");
-      else {
       const long long nodes = (long long)o->B * (o->T + 1);
       const int g1 = (int)((nodes + 255) / 256);
       if (launch_step(o, 0, 0, 0, true, false)) return -1;  // du of the initial guess (k_node_kkt_big)
@@ -895,8 +866,7 @@ int admm_direction(agx_ocp *o, bool prefactor = false) {
         if (iter == 1 || (iter > 2 && (iter - 1) % agx::kRhoInterval == 0))  // Hessian part: first iteration and after a rho update
           hipLaunchKernelGGL((agx::k_admm_tile_big<NV>), dim3((int)nodes), dim3(256), 0, o->stream, o->d_ocp, o->d_qt, o->d_qt2, o->d_aux, o->d_cx,
                              o->d_du, o->d_cjac, o->d_y, o->d_z, o->d_state);
-        hipLaunchKernelGGL((agx::k_riccati_blk<NV>), dim3(o->B), dim3(256), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt2, o->d_Kws, o->d_kws, o->d_dx,
-                           o->d_w, o->d_state, 1, 0);
+        launch_riccati_blk<NV>(o, o->d_qt2, 1, 0);
         hipLaunchKernelGGL((agx::k_admm_update_big<NV>), dim3((int)((nodes + 1) / 2)), dim3(64), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux, o->d_dx,
                            o->d_w, o->d_du, o->d_cx, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_nodestat, o->d_admmstat, o->d_qt2, o->d_state);
         hipLaunchKernelGGL(agx::k_admm_reduce, dim3(o->B), dim3(128), 0, o->stream, o->d_ocp, o->d_admmstat, o->d_state, iter, o->d_ndone + 1);
@@ -919,7 +889,6 @@ int admm_direction(agx_ocp *o, bool prefactor = false) {
                          o->d_Kout, (const DevState *)nullptr);
       HIPCHK(hipGetLastError());
       return 0;
-      }
     } else {
       if constexpr (CH) if (o->con_wide) return admm_direction_nv7<NV, CH, true>(o, prefactor);
       return admm_direction_nv7<NV, CH, false>(o, prefactor);
@@ -1239,10 +1208,7 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   if (const char *e = getenv("AGX_K1_LANES")) o->k1_lanes = (e[0] != '0');
   if (const char *e = getenv("AGX_SPECULATE_GAINS")) o->speculate = (e[0] != '0');
   if (const char *e = getenv("AGX_GAINS_MFMA")) o->gains_mfma = (e[0] != '0');
-  if (const char *e = getenv("AGX_RICCATI_MFMA")) o->riccati_mfma = (e[0] != '0');
-  if (const char *e = getenv("AGX_RICCATI_BLK")) o->riccati_blk = (e[0] != '0');
   if (const char *e = getenv("AGX_RICCATI_MX")) o->riccati_mx = (e[0] != '0');
-  if (const char *e = getenv("AGX_FUSED_KKT")) o->fuse_kkt = (e[0] != '0');
   if (const char *e = getenv("AGX_NO_EMPTY_LAUNCHES")) o->no_empty = (e[0] != '0');
   o->fold_publish = batch <= 204;
   if (const char *e = getenv("AGX_FOLD_PUBLISH")) o->fold_publish = (e[0] != '0');
@@ -1388,7 +1354,7 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   for (int lay = 0; lay < 2; ++lay)
     for (int r = 0; r < o->ho.rows[lay].n; ++r)
       if (o->ho.rows[lay].active[r] && o->ho.rows[lay].act[r] != AGX_ACT_WEIGHTED_QUAD) convex_rows = false;
-  if (o->nv <= 7 && o->riccati_mx && !o->has_con && !o->fuse_kkt && convex_rows) {
+  if (o->nv <= 7 && o->riccati_mx && !o->has_con && convex_rows) {
     // ten segments while the two sweeps of a paired launch (2 B S waves of 254 VGPRs) fit the 2 048 wave slots of the chip
     // at two per SIMD; fewer above that; below five segments the 2.4 x arithmetic is not paid back (measured, B = 256: none)
     int S = std::min(10, 1024 / o->B);

@@ -1,211 +1,18 @@
-// agimus_controller_amd -- large models (nv > 7, e.g. the 30-DoF humanoid of BASELINE configs[4]).
+// agimus_controller_amd -- large models (7 < nv <= 32, e.g. the 30-DoF humanoid of BASELINE configs[4]): the node-parallel kernels.
 //
-// The register-resident kernels map an nv x nv block onto an 8 x 8 lane grid; beyond that the same
-// algebra runs out of LDS: one 256-thread workgroup per instance keeps the 3nv x (3nv + 1) elimination
-// matrix (w | q | v blocks + gradient column) and the value function of node t+1 in LDS
-// (nv = 30: 66 KB + 29 KB) and eliminates the nv acceleration variables with nv Gauss-Jordan pivots,
-// two barriers each.  Same tiles (row stride 32), same acceleration-input QP, same outputs as the
-// nv <= 7 path.  The derivative pass and the line-search trials of these sizes are the
-// workgroup-per-node kernels of agx_big_k1.hpp (LDS + fp64 MFMA, no scratch).
+// Same tiles (row stride 32), same acceleration-input QP, same outputs as the nv <= 7 path, one node (or one instance and
+// node) per wave or workgroup, no recursion over the horizon:
+//   k_node_kkt_big, k_node_kkt_gen        K3: du and the KKT / cost / gap share of every node
+//   k_admm_tile_big, k_admm_update_big    the node kernels of the ADMM loop (constraints, agx_admm.hpp)
+//   k_sigma_tile_big                      the sigma-augmented tiles of the exit path (feedback gains)
+//   k_gains_to_u_big, k_gains_to_u_mfma   K = M Kw - taux
+// The serial part, the Riccati sweep, is k_riccati_blk (agx_big_k2.hpp); the derivative pass and the line-search trials
+// are the workgroup-per-node kernels of agx_big_k1.hpp (LDS + fp64 MFMA, no scratch).
 //
 // (included at the end of agx_kernels.hpp)
 #pragma once
 
 namespace agx {
-
-// K2 for large nv.  gains_pass: backward sweep only, every instance, on the sigma-augmented tiles
-// (k_sigma_tile_big), gradient ignored.
-template <int NV>
-__global__ void __launch_bounds__(256) k_riccati_big(const DevOcp *__restrict__ op, const double *__restrict__ dts,
-                                                     const double *__restrict__ qts, double *__restrict__ Kws,
-                                                     double *__restrict__ kws, double *__restrict__ dxs,
-                                                     double *__restrict__ wss, DevState *__restrict__ st, int forward,
-                                                     int gains_pass) {
-  constexpr int NX = 2 * NV, R = 3 * NV, GC = 3 * NV, CS = 3 * NV + 2;
-  typedef QT<NV> Q;
-  __shared__ double Mx[R * CS];
-  // the value Hessian of node t+1 lives in the x-x block of Mx (rows / columns NV..3NV): the build below
-  // reads exactly the four entries it overwrites, so no second 2nv x 2nv array is needed (69 KB of LDS
-  // in total at nv = 30: two workgroups per CU)
-#define AGX_VV(i, j) Mx[(NV + (i)) * CS + NV + (j)]
-  __shared__ double vx[NX], vp[NX], fl[NX], rpv[NV], dxl[NX], wl[NV];
-  __shared__ double rowbuf[2][3 * NV + 8], colbuf[2][3 * NV + 8];
-  const DevOcp &o = *op;
-  const int T = o.T, b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  DevState &S = st[b];
-  if (!gains_pass && (S.done || S.admm_conv)) return;
-  // gains_pass selects the instances of the sigma sweep like gmode of riccati_body: 1 everyone (agx_ocp_direction, timing),
-  // 2 the fix-up on exit (instances whose last direction has no gains yet), 4 the unfinished instances before the line search of
-  // an iteration the loop may end with (current regularisation).  ls_acc tells k_gains_to_u_* which instances were swept.
-  if (gains_pass) {
-    const bool run = gains_pass == 1 || (gains_pass == 4 && !S.done) || (gains_pass == 2 && S.gains_iter != S.dir_iter);
-    __syncthreads();  // everyone has read the state before it is written
-    if (threadIdx.x == 0) { S.ls_acc = run ? 1 : 0; if (run && gains_pass != 1) S.gains_iter = S.dir_iter; }
-    if (!run) return;
-  }
-  const double dreg = (gains_pass && gains_pass != 4) ? (S.solved ? S.dreg : S.gains_dreg) : S.dreg;
-  const double *qb = qts + (long long)b * (T + 1) * Q::SIZE;
-  double *Kw = Kws + (long long)b * T * NV * NX, *kw = kws + (long long)b * T * NV;
-  // value function of the terminal node
-  {
-    const double *tt = qb + (long long)T * Q::SIZE;
-    for (int e = tid; e < NX * NX; e += nt) {
-      const int i = e / NX, j = e % NX;
-      const int ib = i < NV ? i : i - NV, jb = j < NV ? j : j - NV;
-      double v;
-      if (i < NV && j < NV) v = tt[Q::Hqq + ib * Q::LD + jb];
-      else if (i < NV) v = tt[Q::Hqv + ib * Q::LD + jb];
-      else if (j < NV) v = tt[Q::Hqv + jb * Q::LD + ib];
-      else v = tt[Q::Hvv + ib * Q::LD + jb];
-      AGX_VV(i, j) = v + ((i == j) ? dreg : 0.0);
-    }
-    for (int i = tid; i < NX; i += nt) vx[i] = gains_pass ? 0.0 : tt[Q::gx + i];
-  }
-  __syncthreads();
-  for (int t = T - 1; t >= 0; --t) {
-    const double *tl = qb + (long long)t * Q::SIZE;
-    const double h = dts[t], h2 = h * h;
-    // vp = vx + V f
-    for (int i = tid; i < NX; i += nt) fl[i] = gains_pass ? 0.0 : tl[Q::f + i];
-    __syncthreads();
-    for (int i = tid; i < NX; i += nt) {
-      double s = vx[i];
-      for (int j = 0; j < NX; ++j) s += AGX_VV(i, j) * fl[j];
-      vp[i] = s;
-    }
-    __syncthreads();
-    // elimination matrix: rows / columns  w (0..NV) | q | v, gradient in column GC
-    for (int e = tid; e < NV * NV; e += nt) {
-      const int r = e / NV, c = e % NV;
-      const int rc = r * Q::LD + c, cr = c * Q::LD + r;
-      const double Vqq = AGX_VV(r, c), Vqv = AGX_VV(r, NV + c), Vvq = AGX_VV(NV + r, c), Vvv = AGX_VV(NV + r, NV + c);
-      const double Yq = h2 * Vqq + h * Vvq, Yv = h2 * Vqv + h * Vvv;
-      const double YqT = h2 * Vqq + h * Vqv, YvT = h2 * Vvq + h * Vvv;
-      Mx[r * CS + c] = tl[Q::Hww + rc] + h2 * Yq + h * Yv;
-      Mx[r * CS + NV + c] = tl[Q::Hqw + cr] + Yq;
-      Mx[r * CS + 2 * NV + c] = tl[Q::Hvw + cr] + h * Yq + Yv;
-      Mx[(NV + r) * CS + c] = tl[Q::Hqw + rc] + YqT;
-      Mx[(2 * NV + r) * CS + c] = tl[Q::Hvw + rc] + h * YqT + YvT;
-      Mx[(NV + r) * CS + NV + c] = tl[Q::Hqq + rc] + Vqq;
-      Mx[(NV + r) * CS + 2 * NV + c] = tl[Q::Hqv + rc] + h * Vqq + Vqv;
-      Mx[(2 * NV + r) * CS + NV + c] = tl[Q::Hqv + cr] + h * Vqq + Vvq;
-      Mx[(2 * NV + r) * CS + 2 * NV + c] = tl[Q::Hvv + rc] + h2 * Vqq + h * (Vqv + Vvq) + Vvv;
-    }
-    for (int r = tid; r < NV; r += nt) {
-      const double vpq = vp[r], vpv = vp[NV + r];
-      Mx[r * CS + GC] = gains_pass ? 0.0 : tl[Q::gw + r] + h2 * vpq + h * vpv;
-      Mx[(NV + r) * CS + GC] = gains_pass ? 0.0 : tl[Q::gx + r] + vpq;
-      Mx[(2 * NV + r) * CS + GC] = gains_pass ? 0.0 : tl[Q::gx + NV + r] + h * vpq + vpv;
-    }
-    __syncthreads();
-    // Gauss-Jordan pivots on the w block, register blocked: thread (br, bc) keeps the RB x CB block
-    // rows RB*br.., columns CB*bc.. of the elimination matrix in registers for all nv pivots; per pivot
-    // the owners of row k / column k publish them through (double-buffered) LDS vectors, everybody
-    // reads RB + CB values and does RB*CB FMAs.  The pivot row itself stays as it is (factor 0).
-    {
-      constexpr int NBC = 16, CB = (GC + NBC) / NBC, NBR = 256 / NBC - 1, RB = (R + NBR - 1) / NBR;
-      static_assert(CB * NBC > GC && RB * NBR >= R, "block grid must cover the elimination matrix");
-      const int br = tid / NBC, bc = tid % NBC;
-      const bool owner = br < NBR;
-      double m[RB][CB];
-#pragma unroll
-      for (int i = 0; i < RB; ++i)
-#pragma unroll
-        for (int j = 0; j < CB; ++j) {
-          const int r = RB * br + i, c = CB * bc + j;
-          m[i][j] = (owner && r < R && c <= GC) ? Mx[r * CS + c] : 0.0;
-        }
-      for (int k = 0; k < NV; ++k) {
-        double *rowk = rowbuf[k & 1], *colk = colbuf[k & 1];
-        if (owner && k / RB == br) {
-#pragma unroll
-          for (int i = 0; i < RB; ++i)
-            if (i == k % RB) {
-#pragma unroll
-              for (int j = 0; j < CB; ++j) rowk[CB * bc + j] = m[i][j];
-            }
-        }
-        if (owner && k / CB == bc) {
-#pragma unroll
-          for (int j = 0; j < CB; ++j)
-            if (j == k % CB) {
-#pragma unroll
-              for (int i = 0; i < RB; ++i) colk[RB * br + i] = m[i][j];
-            }
-        }
-        __syncthreads();
-        const double rp = 1.0 / rowk[k];
-        if (tid == 0) rpv[k] = rp;
-        double fi[RB], rj[CB];
-#pragma unroll
-        for (int i = 0; i < RB; ++i) fi[i] = (RB * br + i == k) ? 0.0 : colk[RB * br + i] * rp;
-#pragma unroll
-        for (int j = 0; j < CB; ++j) rj[j] = rowk[CB * bc + j];
-#pragma unroll
-        for (int i = 0; i < RB; ++i)
-#pragma unroll
-          for (int j = 0; j < CB; ++j) m[i][j] -= fi[i] * rj[j];
-      }
-      __syncthreads();
-      // back to LDS: what the rest of the step reads (x columns and the gradient column of every row)
-#pragma unroll
-      for (int i = 0; i < RB; ++i)
-#pragma unroll
-        for (int j = 0; j < CB; ++j) {
-          const int r = RB * br + i, c = CB * bc + j;
-          if (owner && r < R && c >= NV && c <= GC) Mx[r * CS + c] = m[i][j];
-        }
-      __syncthreads();
-    }
-    // gains of this node and the value function of node t
-    for (int e = tid; e < NV * NX; e += nt) {
-      const int r = e / NX, c = e % NX;
-      Kw[(long long)t * NV * NX + e] = Mx[r * CS + NV + c] * rpv[r];
-    }
-    for (int r = tid; r < NV; r += nt) kw[(long long)t * NV + r] = Mx[r * CS + GC] * rpv[r];
-    for (int e = tid; e < NX * NX; e += nt) {  // symmetrise in place: one thread per unordered pair
-      const int i = e / NX, j = e % NX;
-      if (i > j) continue;
-      const double sv = 0.5 * (AGX_VV(i, j) + AGX_VV(j, i)) + ((i == j) ? dreg : 0.0);
-      AGX_VV(i, j) = sv;
-      AGX_VV(j, i) = sv;
-    }
-    for (int i = tid; i < NX; i += nt) vx[i] = Mx[(NV + i) * CS + GC];
-    __syncthreads();
-  }
-  if (gains_pass || !forward) return;
-  // forward pass
-  double *dx = dxs + (long long)b * (T + 1) * NX, *ws = wss + (long long)b * T * NV;
-  for (int i = tid; i < NX; i += nt) { dxl[i] = 0.0; dx[i] = 0.0; }
-  __threadfence_block();
-  __syncthreads();
-  for (int t = 0; t < T; ++t) {
-    const double *tl = qb + (long long)t * Q::SIZE;
-    const double h = dts[t], h2 = h * h;
-    for (int r = tid; r < NV; r += nt) {
-      double s = -kw[(long long)t * NV + r];
-      const double *kr = Kw + ((long long)t * NV + r) * NX;
-      for (int c = 0; c < NX; ++c) s -= kr[c] * dxl[c];
-      wl[r] = s;
-      ws[(long long)t * NV + r] = s;
-    }
-    __syncthreads();
-    double nq = 0.0, nv2 = 0.0;
-    if (tid < NV) {
-      nq = dxl[tid] + h * dxl[NV + tid] + h2 * wl[tid] + tl[Q::f + tid];
-      nv2 = dxl[NV + tid] + h * wl[tid] + tl[Q::f + NV + tid];
-    }
-    __syncthreads();
-    if (tid < NV) {
-      dxl[tid] = nq; dxl[NV + tid] = nv2;
-      dx[(long long)(t + 1) * NX + tid] = nq;
-      dx[(long long)(t + 1) * NX + NV + tid] = nv2;
-    }
-    __syncthreads();
-  }
-}
-
-#undef AGX_VV
 
 // K3 for large nv (see k_node_kkt for the identities): 32 lanes per node, lane l = column l of every matrix row (one
 // coalesced 256-byte row load per matrix and row), the row sums  du_i = sum_l M[i][l] w_l + tq[i][l] dq_l + tv[i][l] dv_l

@@ -1,21 +1,31 @@
-// agx_big_k2.hpp -- K2 for large models (16 < nv <= 32), blocked factorisation on the fp64 matrix cores.
+// agx_big_k2.hpp -- K2 for large models (16 <= nv <= 32), blocked factorisation on the fp64 matrix cores.
 //
-// Same recursion as k_riccati_mfma (agx_big_k1.hpp; mim_solvers SolverCSQP backwardPass / computeDirection as called from
-// agimus_controller/ocp_base_croco.py:172, acceleration-input form of DESIGN.md section 4), one 256-thread workgroup per
-// instance.  What changed is how  Kw = Qww^-1 Qwx  is formed.  k_riccati_mfma eliminates [Qww | a quarter of the right-hand
-// sides] on every wave, a row per lane, 30 pivots whose multipliers travel through v_readlane: 945 column updates of three
-// instructions per wave and node, four times over (the elimination of Qww itself is redundant on every wave), on a
-// chain of 51 nodes.  Here
-//   * wave 0 inverts Qww (padded to 32 x 32 with a unit diagonal) as a 2 x 2 block matrix of 16 x 16 tiles held in the
+// The Riccati recursion of mim_solvers SolverCSQP backwardPass / computeDirection as called from
+// agimus_controller/ocp_base_croco.py:172, in the acceleration-input form of DESIGN.md section 4; one 256-thread workgroup
+// per instance walks the horizon backwards.  Per node t, with V (symmetrised, + dreg I), vx the value function of node t + 1:
+//   * vp = vx + V f;  Qww, Qxw = Qwx', qw, qx from the QP tile and V, element-wise thanks to the (Phi, G) structure of the
+//     acceleration-input QP (coalesced tile reads, one node ahead);  Qxx = Hxx + Phi' V Phi is the start value of the
+//     accumulators of the last step;
+//   * one wave inverts Qww (padded to 32 x 32 with a unit diagonal) as a 2 x 2 block matrix of 16 x 16 tiles held in the
 //     accumulator layout of v_mfma_f64_16x16x4 (lane 16 g + j: column j of rows g + 4 r):
 //         inv11 = A11^-1 (in-place Gauss-Jordan inside the tile: 16 pivots, ~40 instructions each, no LDS)
 //         W = inv11 A12,  S = A22 - A12' W,  invS = S^-1 (16 pivots),
 //         B21 = -invS W',  B11 = inv11 - W B21,  B22 = invS
 //     -- the five tile products are 20 MFMAs with the accumulator-layout registers as operands
-//     (mfma(X[r], Y[r]) summed over r is X' Y, see agx_riccati_mx.hpp);
-//   * every wave then forms its 16 columns of  Kw = Qww^-1 Qwx  on the matrix cores (16 MFMAs, operands from LDS),
-//   * V = Qxx - Qxw Kw as before.
-// The vector part (vp = vx + V f, kw, the gradient of the value function) is spread over four lanes per row.
+//     (mfma(X[r], Y[r]) summed over r is X' Y, see agx_riccati_mx.hpp); nv = 16 is the single tile inv11;
+//   * every wave then forms its 16 columns of  Kw = Qww^-1 Qwx  (kw = Qww^-1 qw is one more column) on the matrix cores:
+//     the product with the inverse (16 MFMAs, operands from LDS), then one step of iterative refinement with Qww itself;
+//   * V = Qxx - Qxw Kw  (2nv x nv x 2nv) on the matrix cores, wave w owns a band of the 16 x 16 result tiles;
+//     vx = qx - Qxw kw.
+// The vector part (vp, kw, the gradient of the value function) is spread over four lanes per row.  The forward pass
+// (forward != 0) is  w = -kw - Kw dx,  dx' = Phi dx + G w + f  from node 0.
+// (Before the blocked inverse every wave eliminated [Qww | its quarter of the right-hand sides] a row per lane, 30 pivots
+// with v_readlane multipliers, the elimination of Qww itself four times over: 482 VGPRs, one workgroup per CU, twice the time.)
+//
+// gains_pass != 0: backward sweep only, on the sigma-augmented tiles (k_sigma_tile_big), gradient ignored -- the feedback
+// gains of the exit path.  Its value selects the instances like gmode of riccati_body: 1 everyone (agx_ocp_direction, timing),
+// 2 the fix-up on exit (instances whose last direction has no gains yet), 4 the unfinished instances before the line search
+// of an iteration the loop may end with (current regularisation).  ls_acc tells k_gains_to_u_* which instances were swept.
 #pragma once
 
 namespace agx {
@@ -103,7 +113,7 @@ __global__ void __launch_bounds__(256, 2) k_riccati_blk(const DevOcp *__restrict
 #endif
   DevState &S = st[b];
   if (!gains_pass && (S.done || S.admm_conv)) return;
-  // gains_pass: as in k_riccati_mfma
+  // gains_pass: which instances this sweep takes (header)
   if (gains_pass) {
     const bool run = gains_pass == 1 || (gains_pass == 4 && !S.done) || (gains_pass == 2 && S.gains_iter != S.dir_iter);
     __syncthreads();  // everyone has read the state before it is written

@@ -1,5 +1,6 @@
 """30-DoF tree (BASELINE.json configs[4], synthetic humanoid of factory/robot_tables.py): the large-model
-kernels (agx_big.hpp: LDS Riccati sweep, scratch-array derivative pass) against the CPU checker."""
+kernels (the workgroup-per-node derivative pass k_calc_qp_wg, the blocked Riccati sweep k_riccati_blk, the node kernels
+of agx_big.hpp) against the CPU checker."""
 import numpy as np
 import pytest
 
@@ -49,7 +50,7 @@ def test_derivative_tiles_30dof(hip_backend, humanoid):
 
 
 def test_direction_30dof(hip_backend, humanoid):
-    """QP tiles (scratch-array K1) + LDS Riccati sweep + KKT shares + exit gains at a fixed point."""
+    """QP tiles (k_calc_qp_wg) + Riccati sweep (k_riccati_blk) + KKT shares + exit gains at a fixed point."""
     frame = len(humanoid.frame_names) - 1
     B, T = 3, 6
     po, ref, x0, xs, us = workloads.random_goal_problem(humanoid, T, 0.01, B, seed=6, frame=frame)
