@@ -87,6 +87,16 @@ struct agx_ocp {
   int mx2_S = 0;
   double *d_mx2_elem = nullptr, *d_mx2_bnd = nullptr, *d_mx2_cl = nullptr;  // [2][B][S][3][256] segment elements, [2][B][S][256] boundary value functions, [B][S][256] transitions under the gains
   bool k1_fused = true;     // AGX_K1_FUSED=0: running and terminal nodes of the derivative pass as two launches (profiling)
+  // Tile carry across MPC steps: the running-node tiles live in a ring (tile_slot, agx_kernels.hpp) whose
+  // origin advances with every carried agx_ocp_mpc_step, so that the first derivative pass of a step evaluates nodes 0, T - 1
+  // and T only.  7-joint capacity, eight-lane derivative kernel, unconstrained, MFMA-layout sweeps, one dt for every node.
+  bool tile_carry = true;       // AGX_TILE_CARRY=0: the full pass every step
+  bool carry_static = false;    // the problem qualifies (agx_ocp_create)
+  bool carry_armed = false;     // the last call that touched the iterate, the references or the tiles was an agx_ocp_mpc_step
+  int carry_k0 = 0;             // ... with this window
+  int head = 0;                 // DevOcp::head as the stream will see it
+  int n_carriable = -1;         // instances whose tiles the next step may inherit, as the last solve published it (-1: not known)
+  bool frames_uniform = true;   // the resident frame table holds one frame per row for every node (no per-node override uploaded)
   // Batch policy (agx_ocp_set_quorum): the SQP loop of a batch step ends once this fraction of the instances has
   // finished, the ADMM loop of an SQP iteration once this fraction of the QPs has converged; the others keep their
   // iterate (solved = 0 / qp_iters = max_qp_iters) and continue from it at the next MPC step, as a lone controller
@@ -118,7 +128,8 @@ struct agx_ocp {
   DevState *d_state = nullptr;
   int *d_ndone = nullptr;
   // pinned, fine-grained (coherent) mapped host words, 64 bit each: [0] finished-instance count, [1] its sequence
-  // stamp, [2] stamp of the packed results, [3] scratch value, [4] ADMM converged count, [5] its stamp.
+  // stamp, [2] stamp of the packed results, [3] scratch value, [4] ADMM converged count, [5] its stamp, [6] / [7] line-search
+  // trials handed on / iterations ended with stale tiles, [8] instances with tiles the next MPC step may inherit.
   // Stamps are 64-bit and only ever grow (no wrap in practice); slots start at ~0, which no stamp takes.
   unsigned long long *h_ndone = nullptr;
   unsigned long long *h_ndone_dev = nullptr;  // the same words as the device sees them (mapped host memory)
@@ -450,7 +461,8 @@ int launch_calc_diff(agx_ocp *o, bool masked, bool running_only = false) {
 // kernel (agx_k1_lanes.hpp); trees fall back to one lane per node.
 // phase 1: the pass runs at the trial iterates (staging halves of xs / us) of the instances in the line search and leaves
 // their tiles in place of the current ones (k_sqp_head / k_sqp_accept, agx_kernels.hpp); nv <= 7 only.
-int launch_calc_qp(agx_ocp *o, bool running_only = false, bool term_only = false, int phase = 0) {
+// compact (phase 0, eight-lane kernel): every instance inherits its tiles (DevState::carry): a grid over nodes 0, T - 1 and T only.
+int launch_calc_qp(agx_ocp *o, bool running_only = false, bool term_only = false, int phase = 0, bool compact = false) {
   return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
@@ -470,19 +482,20 @@ int launch_calc_qp(agx_ocp *o, bool running_only = false, bool term_only = false
     bool lanes = false;
     if constexpr (NV <= 7) lanes = CH && o->k1_lanes && o->lanes_ok;
     if constexpr (NV <= 7) if (lanes) {
-      const int n_run = (int)((units * 8 + 63) / 64), n_term = (int)(((long long)o->B * 8 + 63) / 64);
+      const long long run_nodes = compact ? (long long)o->B * (o->T > 1 ? 2 : 1) : units;
+      const int n_run = (int)((run_nodes * 8 + 63) / 64), n_term = (int)(((long long)o->B * 8 + 63) / 64), cp = compact ? 1 : 0;
 #define AGX_LAUNCH_LJ(COLL)                                                                                                              \
   do {                                                                                                                                   \
     if (o->k1_fused && !term_only && !running_only) { /* both node types in one launch */                                                \
       hipLaunchKernelGGL((agx::k_calc_qp_lj_all<NV, COLL>), dim3(n_run + n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, \
-                         xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, n_run, phase);                                             \
+                         xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, n_run, phase, cp);                                         \
     } else {                                                                                                                             \
       if (!term_only)                                                                                                                    \
         hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, false, COLL>), dim3(n_run), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt,     \
-                           xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase);                                                  \
+                           xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp);                                              \
       if (!running_only)                                                                                                                 \
         hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, true, COLL>), dim3(n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt,     \
-                           xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase);                                                  \
+                           xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp);                                              \
     }                                                                                                                                    \
   } while (0)
       if (o->lanes_coll) AGX_LAUNCH_LJ(true); else AGX_LAUNCH_LJ(false);
@@ -565,10 +578,11 @@ int launch_riccati(agx_ocp *o, int forward, bool pair = false, int iter = 0, con
 // K3 (node shares of the KKT residual, cost, gaps; du) and the head of the step: instance totals, convergence test and the
 // first trial iterate of the line search (the caller runs the trial rounds: line_search_rounds).
 agx::HostWords host_words(agx_ocp *o, bool line_search_counters, unsigned long long seq) {
-  agx::HostWords hw{nullptr, nullptr, nullptr, nullptr, 0};
+  agx::HostWords hw{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   if (!o->poll || !o->fold_publish || seq == 0) return hw;
   hw.done = o->h_ndone_dev + 0;
   if (line_search_counters) { hw.handed = o->h_ndone_dev + 6; hw.stale = o->h_ndone_dev + 7; }
+  hw.carry = o->h_ndone_dev + 8;
   hw.seq = o->h_ndone_dev + 1;
   hw.stamp = seq;
   return hw;
@@ -896,10 +910,23 @@ int admm_direction(agx_ocp *o, bool prefactor = false) {
   });
 }
 
+// Every entry point that changes an input of the derivative pass, the iterate or the tiles outside agx_ocp_mpc_step: the next
+// step runs the full pass, with the tiles back in node order.
+int carry_invalidate(agx_ocp *o) {
+  o->carry_armed = false;
+  if (o->head != 0) {
+    o->head = 0;
+    HIPCHK(hipMemsetAsync((char *)o->d_ocp + offsetof(DevOcp, head), 0, sizeof(int), o->stream));
+  }
+  return 0;
+}
+
 // agx_ocp_refs_activate: the tile staged by agx_ocp_set_refs_async becomes the solver's tile -- the solver's stream waits
 // for the copy (no host wait) and the two device tiles swap roles.
 int adopt_pending_refs(agx_ocp *o) {
   if (!o->refs_pending) return 0;
+  if (carry_invalidate(o)) return -1;
+  if (o->refs_pending_frames) o->frames_uniform = false;
   HIPCHK(hipStreamWaitEvent(o->stream, o->ev_refs, 0));
   std::swap(o->d_ref, o->d_ref_back);
   if (o->refs_pending_frames) std::swap(o->d_frames, o->d_frames_back);
@@ -959,11 +986,12 @@ int line_search_rounds(agx_ocp *o, int it, int max_iter, bool *need_k1, int *n_d
       if (wait_stamp(o, 1, seq)) return -1;  // stored by the last workgroup of k_sqp_accept
     } else if (o->poll) {
       hipLaunchKernelGGL(agx::k_publish3, dim3(1), dim3(1), 0, o->stream, o->d_ndone, o->h_ndone_dev + 0, o->h_ndone_dev + 6, o->h_ndone_dev + 7,
-                         o->h_ndone_dev + 1, seq);
+                         o->h_ndone_dev + 8, o->h_ndone_dev + 1, seq);
       HIPCHK(hipGetLastError());
       if (wait_stamp(o, 1, seq)) return -1;
     } else {
-      o->h_ndone[0] = 0; o->h_ndone[6] = 0; o->h_ndone[7] = 0;
+      o->h_ndone[0] = 0; o->h_ndone[6] = 0; o->h_ndone[7] = 0; o->h_ndone[8] = 0;
+      HIPCHK(hipMemcpyAsync(o->h_ndone + 8, o->d_ndone + 6, sizeof(int), hipMemcpyDeviceToHost, o->stream));
       HIPCHK(hipMemcpyAsync(o->h_ndone, o->d_ndone, sizeof(int), hipMemcpyDeviceToHost, o->stream));
       HIPCHK(hipMemcpyAsync(o->h_ndone + 6, o->d_ndone + 3, sizeof(int), hipMemcpyDeviceToHost, o->stream));
       HIPCHK(hipMemcpyAsync(o->h_ndone + 7, o->d_ndone + 4, sizeof(int), hipMemcpyDeviceToHost, o->stream));
@@ -972,6 +1000,7 @@ int line_search_rounds(agx_ocp *o, int it, int max_iter, bool *need_k1, int *n_d
     *n_done_out = (int)__atomic_load_n(o->h_ndone, __ATOMIC_ACQUIRE);
     const unsigned handed = (unsigned)__atomic_load_n(o->h_ndone + 6, __ATOMIC_ACQUIRE);
     const unsigned stale = (unsigned)__atomic_load_n(o->h_ndone + 7, __ATOMIC_ACQUIRE);
+    o->n_carriable = (int)__atomic_load_n(o->h_ndone + 8, __ATOMIC_ACQUIRE);
     const bool more = handed != o->ls_handed;
     if (stale != o->ls_stale) *need_k1 = true;
     o->ls_handed = handed;
@@ -982,9 +1011,11 @@ int line_search_rounds(agx_ocp *o, int it, int max_iter, bool *need_k1, int *n_d
 }
 
 // The SQP loop of SolverCSQP::solve on the resident buffers.
-int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done = false) {
+// carry_mode (agx_ocp_mpc_step): 0 no instance inherits tiles, 1 some do (k_mpc_prologue has decided: DevState::carry), 2 all do.
+int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done = false, int carry_mode = 0) {
   if (max_iter <= 0) max_iter = 1000;
   o->last_max_iter = max_iter;
+  o->n_carriable = -1;
   auto t0 = std::chrono::steady_clock::now();
   if (!prologue_done) {  // k_mpc_prologue has reset the state and pinned x0 already
     if (reset_state(o)) return -1;
@@ -1003,7 +1034,11 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
     // derivative pass: running and terminal nodes in one launch; under agx_ocp_profile the running
     // nodes get their own launch so that the kernel the roofline is quoted on is timed alone
     if (need_k1) {
-      if (o->prof && it == 0) {
+      if (it == 0 && carry_mode != 0) {
+        // inherited tiles: nodes 0, T - 1 and T of every carrying instance -- on a grid of just those when everybody carries.
+        // Never the launch the roofline is quoted on (prof_mark 0 stands for a pass over all B T running nodes).
+        if (launch_calc_qp(o, false, false, 0, carry_mode == 2)) return -1;
+      } else if (o->prof && it == 0) {
         if (prof_mark(o, 0, true)) return -1;
         if (launch_calc_qp(o, true, false)) return -1;
         if (prof_mark(o, 0, false)) return -1;
@@ -1039,10 +1074,12 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
     if (o->poll && o->fold_publish && it >= 1) {
       if (wait_stamp(o, 1, seq_head)) return -1;
       n_done = (int)__atomic_load_n(o->h_ndone, __ATOMIC_ACQUIRE);
+      o->n_carriable = (int)__atomic_load_n(o->h_ndone + 8, __ATOMIC_ACQUIRE);
       searching = n_done < o->B;
     } else if (o->prof || o->no_empty) {  // timing / profiling runs: no launches that find nothing to do
       if (read_int(o, o->d_ndone, 0, 1, &n_done)) return -1;
       searching = n_done < o->B;
+      if (!searching && read_int(o, o->d_ndone + 6, 8, 1, &o->n_carriable)) return -1;  // (the line search would have brought it)
     }
     if (searching && line_search_rounds(o, it, max_iter, &need_k1, &n_done)) return -1;
     if (last) { need_fixup = need_fixup || !pair; break; }
@@ -1214,6 +1251,7 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   if (const char *e = getenv("AGX_FOLD_PUBLISH")) o->fold_publish = (e[0] != '0');
   if (const char *e = getenv("AGX_ADMM_LOOP")) { o->admm_loop = (e[0] != '0'); o->admm_loop_always = (e[0] == '2'); }
   if (const char *e = getenv("AGX_K1_FUSED")) o->k1_fused = (e[0] != '0');
+  if (const char *e = getenv("AGX_TILE_CARRY")) o->tile_carry = (e[0] != '0');
   o->T = d->horizon; o->B = batch; o->device = device;
   {
     int n = 0;
@@ -1364,6 +1402,11 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
     while (S >= 2 && o->T / S < 4) --S;  // segments of at least four nodes
     o->mx2_S = S >= 2 ? S : 0;
   }
+  {
+    bool one_dt = true;  // nodes with dt_i != dt_0 are re-integrated by the warm-start shift: not the old node's inputs
+    for (int t = 0; t < o->T; ++t) one_dt = one_dt && o->dt[t] == o->dt[0];
+    o->carry_static = o->tile_carry && o->nv <= 7 && o->chain && o->k1_lanes && o->lanes_ok && o->riccati_mx && !o->has_con && !o->general && one_dt;
+  }
   // probe that a kernel instantiation exists
   if (dispatch(o->nv, o->chain, [](auto, auto) -> int { return 0; })) { delete o; return -1; }
   if (set_device(o)) { delete o; return -1; }
@@ -1420,12 +1463,12 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
 #undef ALLOC
   // the polled hand-off needs FINE-GRAINED host memory (the stamp must not overtake the data it guards): ask for it
   // explicitly; when the runtime cannot give it, fall back to stream-ordered copies + synchronize
-  if (hipHostMalloc((void **)&o->h_ndone, 8 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+  if (hipHostMalloc((void **)&o->h_ndone, 16 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
     (void)hipGetLastError();
     o->poll = false;
-    if (hipHostMalloc((void **)&o->h_ndone, 8 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { agx_ocp_destroy(o); return fail("hipHostMalloc failed"); }
+    if (hipHostMalloc((void **)&o->h_ndone, 16 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { agx_ocp_destroy(o); return fail("hipHostMalloc failed"); }
   }
-  std::memset(o->h_ndone, 0xff, 8 * sizeof(unsigned long long));
+  std::memset(o->h_ndone, 0xff, 16 * sizeof(unsigned long long));
   if (o->poll && hipHostGetDevicePointer((void **)&o->h_ndone_dev, o->h_ndone, 0) != hipSuccess) o->poll = false;
   if (const char *e = getenv("AGX_HOST_POLL")) o->poll = o->poll && (e[0] != '0');
   if (hipMemcpy(o->d_model, &o->hm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess ||
@@ -1518,6 +1561,7 @@ int agx_ocp_set_geom_placement(agx_ocp *o, int frame, const double *se3) {
   if (!o || !se3) return fail("agx_ocp_set_geom_placement: null argument");
   if (frame < 0 || frame >= o->hm.nframes) return fail("agx_ocp_set_geom_placement: frame out of range");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   std::memcpy(o->hm.frame_placement[frame], se3, sizeof(double) * 12);
   // in-stream update of the one placement inside the resident model
   HIPCHK(hipMemcpyAsync((char *)o->d_model + offsetof(DevModel, frame_placement) + sizeof(double) * 12 * frame, o->hm.frame_placement[frame],
@@ -1529,6 +1573,8 @@ int agx_ocp_set_geom_placement(agx_ocp *o, int frame, const double *se3) {
 int agx_ocp_set_refs(agx_ocp *o, const double *ref_tile, const int32_t *frame_ids) {
   if (!o || !ref_tile) return fail("agx_ocp_set_refs: null argument");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
+  if (frame_ids) o->frames_uniform = false;
   if (o->refs_pending) { HIPCHK(hipEventSynchronize(o->ev_refs)); o->refs_pending = false; }  // superseded
   const size_t n = (size_t)o->B * (o->T + 1);
   if (o->padded) {  // the caller's tile is laid out for nvu joints
@@ -1550,6 +1596,8 @@ int agx_ocp_set_refs(agx_ocp *o, const double *ref_tile, const int32_t *frame_id
 int agx_ocp_set_refs_device(agx_ocp *o, const double *d_ref_tile, const int32_t *d_frame_ids, int adopt) {
   if (!o || !d_ref_tile) return fail("agx_ocp_set_refs_device: null argument");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
+  if (d_frame_ids) o->frames_uniform = false;
   const size_t n = (size_t)o->B * (o->T + 1);
   if (o->padded) {  // a device tile in the caller's layout: through the host (padded models are not the fast path)
     std::vector<double> tmp(n * o->stride_u);
@@ -1590,6 +1638,7 @@ int agx_host_free(void *p) {
 int agx_ocp_set_refs_async(agx_ocp *o, const double *ref_tile, const int32_t *frame_ids) {
   if (!o || !ref_tile) return fail("agx_ocp_set_refs_async: null argument");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   if (ensure_copy_stream(o)) return -1;
   const size_t n = (size_t)o->B * (o->T + 1);
   if (!o->d_ref_back) HIPCHK(hipMalloc((void **)&o->d_ref_back, sizeof(double) * n * o->stride));
@@ -1672,6 +1721,7 @@ int agx_ocp_upload_x0(agx_ocp *o, const double *x0) {
 int agx_ocp_upload_warmstart(agx_ocp *o, const double *xs_ws, const double *us_ws) {
   if (!o || !xs_ws || !us_ws) return fail("agx_ocp_upload_warmstart: null argument");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   if (up(o, o->d_xs, xs_ws, (size_t)o->B * (o->T + 1), 2)) return -1;
   if (up(o, o->d_us, us_ws, (size_t)o->B * o->T, 1)) return -1;
   HIPCHK(hipStreamSynchronize(o->stream));
@@ -1681,6 +1731,7 @@ int agx_ocp_upload_warmstart(agx_ocp *o, const double *xs_ws, const double *us_w
 int agx_ocp_solve_resident(agx_ocp *o, int max_iter, double max_time) {
   if (!o) return fail("null handle");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   return solve_resident(o, max_iter, max_time);
 }
 
@@ -1782,7 +1833,7 @@ int agx_ocp_solve(agx_ocp *o, const double *x0, const double *xs_ws, const doubl
                   double *xs, double *us, double *K, agx_status *st) {
   if (!o || !x0 || !xs_ws || !us_ws) return fail("agx_ocp_solve: null argument");
   if (agx_ocp_upload_x0(o, x0)) return -1;
-  if (agx_ocp_upload_warmstart(o, xs_ws, us_ws)) return -1;
+  if (agx_ocp_upload_warmstart(o, xs_ws, us_ws)) return -1;  // (ends the tile carry: carry_invalidate)
   if (solve_resident(o, max_iter, max_time)) return -1;
   return agx_ocp_download(o, xs, us, K, st);
 }
@@ -1790,6 +1841,7 @@ int agx_ocp_solve(agx_ocp *o, const double *x0, const double *xs_ws, const doubl
 int agx_ocp_shift_warmstart(agx_ocp *o) {
   if (!o) return fail("null handle");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
@@ -1971,6 +2023,7 @@ int agx_ocp_calc_diff(agx_ocp *o, double *tiles) {
 int agx_ocp_direction(agx_ocp *o, double *K, double *k, double *dx, double *du, double *kkt) {
   if (!o) return fail("null handle");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   if (reset_state(o)) return -1;
   if (launch_calc_qp(o)) return -1;
   if (launch_riccati(o, 1, 0)) return -1;
@@ -1995,7 +2048,8 @@ int agx_ocp_qp_tiles(agx_ocp *o, double *qt, double *aux, int *qt_size, int *aux
   if (qt_size) *qt_size = o->qt_size;
   if (aux_size) *aux_size = o->aux_size;
   if (!qt && !aux) return 0;
-  if (reset_state(o)) return -1;
+  if (carry_invalidate(o)) return -1;
+  if (reset_state(o)) return -1;  // (and with the ring back at its origin the tiles below come out in node order)
   if (launch_calc_qp(o)) return -1;
   const size_t n = (size_t)o->B * (o->T + 1);
   if (qt) HIPCHK(hipMemcpyAsync(qt, o->d_qt, sizeof(double) * n * o->qt_size, hipMemcpyDeviceToHost, o->stream));
@@ -2019,6 +2073,7 @@ int agx_ocp_time_kernel(agx_ocp *o, int which, int reps, double *avg_ms) {
   if (!o || !avg_ms || reps < 1) return fail("agx_ocp_time_kernel: bad argument");
   if (set_device(o)) return -1;
   // state for the timed kernel: fresh solver state, QP tiles and a direction at the resident point
+  if (carry_invalidate(o)) return -1;
   if (reset_state(o)) return -1;
   if (which == 1 || which == 2 || which == 5 || which == 6 || which == 7) { if (launch_calc_qp(o)) return -1; }
   if (which == 2) { if (launch_riccati(o, 1, 0)) return -1; }
@@ -2073,6 +2128,7 @@ static int traj_frames(agx_ocp *o, int frame) {
   HIPCHK(hipMemcpyAsync(o->d_frames, fr.data(), sizeof(int) * fr.size(), hipMemcpyHostToDevice, o->stream));
   HIPCHK(hipStreamSynchronize(o->stream));
   o->frames_set = true;
+  o->frames_uniform = true;
   return 0;
 }
 
@@ -2084,6 +2140,7 @@ int agx_traj_sine_create(agx_ocp *o, int n_points, double dt, const double *q0, 
   if (n_points < o->T + 1) return fail("agx_traj_sine_create: need at least T+1 samples");
   if (frame < 0 || frame >= o->hm.nframes) return fail("agx_traj_sine_create: frame id out of range");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   const size_t B = o->B, nv = o->nv;
   if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
   if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
@@ -2125,6 +2182,7 @@ int agx_traj_generic_create(agx_ocp *o, int n_points, const double *q, const dou
   if (n_points < o->T + 1) return fail("agx_traj_generic_create: trajectory shorter than the horizon");
   if (frame < 0 || frame >= o->hm.nframes) return fail("agx_traj_generic_create: frame id out of range");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   const size_t B = o->B, nv = o->nv, n = B * (size_t)n_points * nv;
   if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
   if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
@@ -2167,6 +2225,7 @@ int agx_traj_cartesian_sine_create(agx_ocp *o, int n_points, double dt, const do
   if (!(scale_duration > 0.0) || !(precision > 0.0) || it_max < 1) return fail("agx_traj_cartesian_sine_create: scale_duration, precision, it_max must be positive");
   if (o->nv > 7) return fail("agx_traj_cartesian_sine_create: nv <= 7");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   const size_t B = o->B, nv = o->nv, n = B * (size_t)n_points * nv;
   if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
   if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
@@ -2231,6 +2290,7 @@ int agx_traj_cartesian_sine_create(agx_ocp *o, int n_points, double dt, const do
 int agx_traj_set_horizon_indexes(agx_ocp *o, const int32_t *idx) {
   if (!o) return fail("null handle");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   o->hidx.clear();
   if (!idx) return 0;  // back to uniform
   bool uniform = true;
@@ -2303,6 +2363,7 @@ static int ws_from_ref(agx_ocp *o, int k0, int set_x0) {
 int agx_traj_warmstart_from_reference(agx_ocp *o) {
   if (!o || !o->d_pts) return fail("agx_traj_warmstart_from_reference: no resident trajectory");
   if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
   return ws_from_ref(o, o->win_k0, 1);
 }
 
@@ -2340,19 +2401,29 @@ int agx_ocp_mpc_step(agx_ocp *o, int k0, int max_iter, int first) {
   if (set_device(o)) return -1;
   if (agx_traj_set_window(o, k0)) return -1;
   bool prologue_done = false;
+  // Tile carry: this step follows the previous one by one sample on the resident trajectory, so after the shift below node t
+  // has bit for bit the inputs node t + 1 had (iterate, reference sample, dt) for t = 0 .. T - 2; x0 may differ: node 0 is
+  // always evaluated.  Instances decide for themselves in the prologue (tiles of their final iterate, starting regularisation).
+  const size_t lds = sizeof(double) * (size_t)o->T * (o->nx + o->nu);
+  const bool one_launch = o->nv <= 8 && lds <= 60 * 1024;
+  const bool carry = o->carry_static && o->carry_armed && first != 1 && k0 == o->carry_k0 + 1 && one_launch && o->hidx.empty() && o->frames_uniform;
+  const int carry_mode = !carry ? 0 : (o->n_carriable == o->B ? 2 : 1);
+  if (!carry && carry_invalidate(o)) return -1;
+  o->carry_armed = false;  // until this step has gone through
   if (first == 1) {
     if (ws_from_ref(o, k0, 1)) return -1;
   } else {
     // x0 <- xs[1] (first == 0; first == 2: x0 was set by the caller / the feedback rollout), warm-start
     // shift, x0 pin and state reset: one launch when the shifted nodes of an instance fit in LDS
-    const size_t lds = sizeof(double) * (size_t)o->T * (o->nx + o->nu);
-    if (o->nv <= 8 && lds <= 60 * 1024) {
+    if (one_launch) {
+      if (carry) o->head = (o->head + 1) % o->T;
       int rc = dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
         constexpr int NV = decltype(NVc)::value;
         constexpr bool CH = decltype(CHc)::value;
         if constexpr (NV <= 8) {
           hipLaunchKernelGGL((agx::k_mpc_prologue<NV, CH>), dim3(o->B), dim3(128), lds, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
-                             o->d_us, o->d_x0, o->d_state, o->d_ndone, first == 0 ? 1 : 0);
+                             o->d_us, o->d_x0, o->d_state, o->d_ndone, first == 0 ? 1 : 0, carry ? 1 : 0, o->head,
+                             (int *)((char *)o->d_ocp + offsetof(DevOcp, head)));
           HIPCHK(hipGetLastError());
         }
         return 0;
@@ -2364,7 +2435,10 @@ int agx_ocp_mpc_step(agx_ocp *o, int k0, int max_iter, int first) {
       if (agx_ocp_shift_warmstart(o)) return -1;
     }
   }
-  return solve_resident(o, max_iter, 0.0, prologue_done);
+  if (solve_resident(o, max_iter, 0.0, prologue_done, carry_mode)) return -1;
+  o->carry_armed = o->carry_static;
+  o->carry_k0 = k0;
+  return 0;
 }
 
 }  // extern "C"

@@ -346,7 +346,7 @@ __device__ __forceinline__ void riccati_vec_body(const int b, const DevOcp *__re
       for (int i = 0; i < 4; ++i) step(n[i], t - i);
     }
   }
-  riccati_forward<NV>(b, T, dts, qb, Kw, kw, dxs, wss, s_dt);
+  riccati_forward<NV>(o, b, T, dts, qb, Kw, kw, dxs, wss, s_dt);
 }
 
 // ---------------------------------------------------------------------------

@@ -85,7 +85,8 @@ struct DevCons {
 };
 
 struct DevOcp {
-  int T, B, stride, pad;
+  int T, B, stride;
+  int head;  // ring origin of the running-node tiles (tile_slot, agx_kernels.hpp); 0 wherever tiles are not carried across MPC steps
   DevRows rows[2];  // 0 running, 1 terminal
   double tol, mu_dyn, mu_con;
   DevCons cons[2];

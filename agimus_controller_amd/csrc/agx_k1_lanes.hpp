@@ -116,7 +116,7 @@ __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds
                                                 const DevOcp *__restrict__ op, const double *__restrict__ dts,
                                                 const double *__restrict__ xs, const double *__restrict__ us, const RefView &rv,
                                                 double *__restrict__ qts, double *__restrict__ auxs,
-                                                const DevState *__restrict__ st, const int phase) {
+                                                const DevState *__restrict__ st, const int phase, const int compact) {
   constexpr int NX = 2 * NV;
   typedef QT<NV> Q;
   typedef AUX<NV> A;
@@ -125,12 +125,16 @@ __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds
   const int T = o.T;
   const int l8 = threadIdx.x & 7;
   LjNode &L = lds[threadIdx.x >> 3];
-  const long long n_nodes = TERM ? (long long)o.B : (long long)o.B * T;
+  // compact: the grid holds only the running nodes an instance with inherited tiles (DevState::carry) evaluates, 0 and T - 1
+  const int n_per = compact ? (T > 1 ? 2 : 1) : T;
+  const long long n_nodes = TERM ? (long long)o.B : (long long)o.B * n_per;
   const long long node = (blk * blockDim.x + threadIdx.x) >> 3;
   const bool node_ok = node < n_nodes;
   const long long nid = node_ok ? node : 0;  // out-of-range groups shadow node 0 and store nothing
-  const int b = TERM ? (int)nid : (int)(nid / T), t = TERM ? T : (int)(nid % T);
-  const bool act = node_ok && k1_active(st[b], phase);  // phase 1: the trial points of the instances in the line search
+  const int b = TERM ? (int)nid : (int)(nid / n_per), tn = TERM ? 0 : (int)(nid % n_per);
+  const int t = TERM ? T : ((compact && tn) ? T - 1 : tn);
+  // phase 1: the trial points of the instances in the line search; carry: every other running node keeps the tile it has
+  const bool act = node_ok && k1_active(st[b], phase) && (TERM || !st[b].carry || t == 0 || t == T - 1);
   if (!__any(act)) return;  // the whole wave (= workgroup) belongs to instances this pass skips
   const bool jl = l8 < NV;       // lane carries a joint
   const int j = jl ? l8 : NV - 1;
@@ -139,8 +143,9 @@ __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds
   const double *xp = xs + ((long long)b * (T + 1) + t) * NX;
   const double qj = xp[j], vj = jl ? xp[NV + j] : 0.0;
   const double uj = TERM ? 0.0 : us[((long long)b * T + t) * NV + j];
-  double *qt = qts + ((long long)b * (T + 1) + t) * Q::SIZE;
-  double *ax = auxs + ((long long)b * (T + 1) + t) * A::SIZE;
+  const long long sid = (long long)b * (T + 1) + tile_slot(o, t);
+  double *qt = qts + sid * Q::SIZE;
+  double *ax = auxs + sid * A::SIZE;
   const DevRows &rows = o.rows[TERM ? 1 : 0];
   const bool wr = act && jl;  // this lane stores
 
@@ -688,10 +693,10 @@ template <int NV, bool TERM, bool COLL = false>
 __global__ void __launch_bounds__(64, AGX_K1_WAVES) k_calc_qp_lj(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                     const double *__restrict__ dts, const double *__restrict__ xs,
                                                     const double *__restrict__ us, RefView rv, double *__restrict__ qts,
-                                                    double *__restrict__ auxs, const DevState *__restrict__ st, int phase) {
+                                                    double *__restrict__ auxs, const DevState *__restrict__ st, int phase, int compact) {
   __shared__ LjNode lds[8];  // one wave per workgroup: 8 nodes
   __shared__ LjModel lmod;
-  calc_qp_lj_body<NV, TERM, COLL>(blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase);
+  calc_qp_lj_body<NV, TERM, COLL>(blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact);
 }
 
 // The derivative pass of one SQP iteration in ONE launch: the first n_run workgroups take the running
@@ -702,13 +707,13 @@ __global__ void __launch_bounds__(64, AGX_K1_WAVES) k_calc_qp_lj_all(const DevMo
                                                         const double *__restrict__ dts, const double *__restrict__ xs,
                                                         const double *__restrict__ us, RefView rv, double *__restrict__ qts,
                                                         double *__restrict__ auxs, const DevState *__restrict__ st, int n_run,
-                                                        int phase) {
+                                                        int phase, int compact) {
   __shared__ LjNode lds[8];
   __shared__ LjModel lmod;
   if ((int)blockIdx.x < n_run)
-    calc_qp_lj_body<NV, false, COLL>(blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase);
+    calc_qp_lj_body<NV, false, COLL>(blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact);
   else
-    calc_qp_lj_body<NV, true, COLL>((long long)blockIdx.x - n_run, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase);
+    calc_qp_lj_body<NV, true, COLL>((long long)blockIdx.x - n_run, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact);
 }
 
 // Constraint values, Jacobian rows and the l1 violation of every node (k_con_eval, agx_admm.hpp) with 8 lanes per node for the

@@ -35,13 +35,22 @@ struct DevState {
   int searching;                 // the instance is inside the line search of the current SQP iteration
   int ls_n;                      // index of the trial in flight: step length 2^-ls_n
   int tiles_ok;                  // QP / aux tiles (and the constraint data) belong to the current (xs, us): the derivative pass skips it
-  int pad_ls;
+  int carry;                     // this MPC step inherits the tiles of nodes 1 .. T-1 of the previous solve as its nodes 0 .. T-2 (k_mpc_prologue sets it,
+                                 // the head of the first iteration clears it): the first derivative pass evaluates nodes 0, T-1 and T only
   double preg_trial;             // control regularisation the NEXT iteration runs with if the trial in flight is accepted (baked into its tiles)
+  int carry_counted, pad_cc;     // this instance is counted in n_done[6] (instances whose tiles the next MPC step may inherit)
 };
 // which instances a derivative pass (K1, k_con_eval) works on: phase 0 = start of an SQP iteration (everyone whose tiles are
 // stale), phase 1 = the trial points of the instances that are searching (their tiles are overwritten in place)
 __device__ __forceinline__ bool k1_active(const DevState &S, int phase) { return phase ? (S.searching != 0) : (!S.done && !S.tiles_ok); }
 __device__ __forceinline__ double k1_preg(const DevState &S, int phase) { return phase ? S.preg_trial : S.preg; }
+// Physical slot of node t in the per-instance arrays of QP / aux tiles (nv <= 7).  The running nodes form a ring whose origin
+// advances by one node per carried MPC step (agx_ocp_mpc_step), so that the tiles of the old nodes 1 .. T-1 are the new nodes
+// 0 .. T-2 without a copy; the terminal tile keeps slot T.  head == 0 (always, where tiles are not carried): the identity.
+__device__ __forceinline__ int tile_slot(const DevOcp &o, int t) {
+  const int s = t + o.head;
+  return t >= o.T ? t : (s >= o.T ? s - o.T : s);
+}
 
 // Addressing of the reference tiles (host tile or a window of the resident trajectory).
 struct RefView {
@@ -63,6 +72,13 @@ namespace agx {
 constexpr double kSigma = 1e-6;   // SolverCSQP proximal weight
 constexpr double kRegMin = 1e-9;  // crocoddyl reg_min
 constexpr double kRegMax = 1e9;
+
+// An instance's tiles can be inherited by the next MPC step when they belong to its iterate and the control regularisation baked
+// into them (k1_preg: the only solver state a tile depends on) is the one every solve starts with.  n_done[6] counts such instances.
+__device__ __forceinline__ void count_carriable(DevState &S, int *n_done) {
+  const int c = (S.tiles_ok && S.preg == kRegMin) ? 1 : 0;
+  if (c != S.carry_counted) { atomicAdd(n_done + 6, c - S.carry_counted); S.carry_counted = c; }
+}
 
 // ---------------------------------------------------------------------------
 // K1: derivative pass over the running nodes.  unit = b*T + t, one lane each.
@@ -267,8 +283,8 @@ __device__ __forceinline__ void calc_qp_body(const long long unit, const DevMode
   const double *up = us + ((long long)b * T + t) * NU;
 #pragma unroll
   for (int i = 0; i < NU; ++i) u[i] = up[i];
-  double *qt = qts + ((long long)b * (T + 1) + t) * Q::SIZE;
-  double *ax = auxs + ((long long)b * (T + 1) + t) * A::SIZE;
+  double *qt = qts + ((long long)b * (T + 1) + tile_slot(o, t)) * Q::SIZE;
+  double *ax = auxs + ((long long)b * (T + 1) + tile_slot(o, t)) * A::SIZE;
 
   Kin<NV> k;
   kinematics<NV, CHAIN>(m, x, k);
@@ -533,7 +549,7 @@ __device__ __forceinline__ double fast_rcp(double x) {
 // Per node: two FMAs, a DPP row reduction (w = -kw - Kw dx), the lane-local state update and one
 // transposing broadcast of the new state (row r's value to every lane of column r).
 template <int NV>
-__device__ __forceinline__ void riccati_forward(const int b, const int T, const double *__restrict__ dts, const double *__restrict__ qb,
+__device__ __forceinline__ void riccati_forward(const DevOcp &o, const int b, const int T, const double *__restrict__ dts, const double *__restrict__ qb,
                                                 const double *__restrict__ Kw, const double *__restrict__ kw,
                                                 double *__restrict__ dxs, double *__restrict__ wss, const double *s_dt) {
   constexpr int NX = 2 * NV, TS = QT<NV>::SIZE;
@@ -557,8 +573,9 @@ __device__ __forceinline__ void riccati_forward(const int b, const int T, const 
     g.kq = kr[cc];  // lanes outside the block load element [0] of their row / column and are masked at the use: a
     g.kv = kr[NV + cc];  // conditional load is a branch, and the join behind it puts register copies on the loop latch
     g.kw = kw[(long long)t * NV + rr];
-    g.fq = qb[(long long)t * TS + Q::f + rr];
-    g.fv = qb[(long long)t * TS + Q::f + NV + rr];
+    const double *tl = qb + (long long)tile_slot(o, t) * TS;
+    g.fq = tl[Q::f + rr];
+    g.fv = tl[Q::f + NV + rr];
   };
   auto row_sum = [](double p) { p += dpp_xor1(p); p += dpp_xor2(p); p += dpp_xor4(p); return p; };
   auto fstep = [&](Gain &g, int t) {
@@ -672,7 +689,7 @@ __device__ __forceinline__ void riccati_body(const int b, const DevOcp *__restri
   __shared__ double s_aux[GAINS ? 2 : 1][GAINS ? AXN : 1];
   double axr0 = 0.0, axr1 = 0.0, axr2 = 0.0;
   auto aux_fetch = [&](int t) {
-    const double *al = ab + (long long)t * A::SIZE + A::M;
+    const double *al = ab + (long long)tile_slot(o, t) * A::SIZE + A::M;
     axr0 = (lane < AXN) ? al[lane] : 0.0;
     axr1 = (64 + lane < AXN) ? al[64 + lane] : 0.0;
     axr2 = (128 + lane < AXN) ? al[128 + lane] : 0.0;
@@ -684,7 +701,7 @@ __device__ __forceinline__ void riccati_body(const int b, const DevOcp *__restri
     if (128 + lane < AXN) sa[128 + lane] = axr2;
   };
   auto load_tile = [&](Tile &z, int t) {
-    const double *tl = qb + (long long)t * TS;
+    const double *tl = qb + (long long)tile_slot(o, t) * TS;
     z.hqq = tl[Q::Hqq + rc]; z.hqv = tl[Q::Hqv + rc]; z.hvq = tl[Q::Hqv + cr]; z.hvv = tl[Q::Hvv + rc];
     z.hqw = tl[Q::Hqw + rc]; z.hvw = tl[Q::Hvw + rc]; z.hwq = tl[Q::Hqw + cr]; z.hwv = tl[Q::Hvw + cr];
     z.hww = tl[Q::Hww + rc];
@@ -856,7 +873,7 @@ AGX_UNROLL_NV
     if (STORE && any_bad) return;  // no forward pass on gains that were not computed
   }
   if (GAINS || !forward) return;
-  riccati_forward<NV>(b, T, dts, qb, Kw, kw, dxs, wss, s_dt);
+  riccati_forward<NV>(o, b, T, dts, qb, Kw, kw, dxs, wss, s_dt);
 }
 
 template <int NV, bool GAINS>
@@ -921,8 +938,9 @@ __global__ void __launch_bounds__(256) k_node_kkt(const DevOcp *__restrict__ op,
   const double preg = S.preg, dreg = S.dreg;
   const bool jl = l8 < NV;
   const int jj = jl ? l8 : 0;
-  const double *qt = qts + nid * Q::SIZE;
-  const double *ax = auxs + nid * A::SIZE;
+  const long long sid = (long long)b * (T + 1) + tile_slot(o, t);
+  const double *qt = qts + sid * Q::SIZE;
+  const double *ax = auxs + sid * A::SIZE;
   const double *dx = dxs + nid * NX;
   const double dq = jl ? dx[jj] : 0.0, dv = jl ? dx[NV + jj] : 0.0;
   double kkt = 0.0, gap = 0.0;
@@ -1025,7 +1043,7 @@ __device__ __forceinline__ void write_trial_iterate(const DevOcp &o, int b, doub
 // one-thread kernel (a thousand workgroups arriving at one counter cost the B = 1024 step more than the launch: measured).
 // One thread per workgroup calls this, after its last write to the counters.
 struct HostWords {
-  unsigned long long *done, *handed, *stale, *seq;  // mapped host words (handed / stale may be null)
+  unsigned long long *done, *handed, *stale, *carry, *seq;  // mapped host words (handed / stale may be null)
   unsigned long long stamp;
 };
 __device__ __forceinline__ void arrive_and_publish(int *__restrict__ counts, const HostWords &hw) {
@@ -1038,6 +1056,7 @@ __device__ __forceinline__ void arrive_and_publish(int *__restrict__ counts, con
   __hip_atomic_store(hw.done, (unsigned long long)(unsigned)__hip_atomic_load(counts + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (hw.handed) __hip_atomic_store(hw.handed, (unsigned long long)(unsigned)__hip_atomic_load(counts + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (hw.stale) __hip_atomic_store(hw.stale, (unsigned long long)(unsigned)__hip_atomic_load(counts + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(hw.carry, (unsigned long long)(unsigned)__hip_atomic_load(counts + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __threadfence_system();
   __hip_atomic_store(hw.seq, hw.stamp, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -1082,6 +1101,7 @@ __global__ void __launch_bounds__(128) k_sqp_head(const DevOcp *__restrict__ op,
     const double cc = red[2] + red[3], gg = red[4] + red[5], vv = red[6] + red[7];
     kk = fmax(kk, vv);  // checkKKTConditions: KKT = max(KKT, constraint_norm)
     const int dir_fail = S.dir_fail;
+    S.carry = 0;  // inherited tiles served the first derivative pass of the solve only
     if (dir_fail) kk = __builtin_nan("");  // discarded direction: its KKT residual is undefined (never "converged")
     S.kkt = kk; S.cost = cc; S.gap = gg; S.con = vv; S.merit = cc + o.mu_dyn * gg + o.mu_con * vv;
     S.qp_iters = o.has_con ? S.admm_iter : 1;
@@ -1090,7 +1110,7 @@ __global__ void __launch_bounds__(128) k_sqp_head(const DevOcp *__restrict__ op,
     if (!(kk == kk)) S.flags |= 1;
     const bool conv = (kk <= o.tol) && (mode & 1) && !(mode & 4);
     int what = 0;  // 0: nothing more, 1: line search starts
-    if (conv) { S.solved = 1; S.done = 1; S.iter = iter; atomicAdd(n_done, 1); }
+    if (conv) { S.solved = 1; S.done = 1; S.iter = iter; S.tiles_ok = 1; atomicAdd(n_done, 1); }  // (the tiles are those of the final iterate)
     else if ((mode & 1) && !(mode & 4)) {
       S.tiles_ok = 0;
       if (dir_fail) { S.flags |= 4; sqp_iteration_end(S, false, 1.0 / 512.0, iter, max_iter, n_done); }
@@ -1105,6 +1125,7 @@ __global__ void __launch_bounds__(128) k_sqp_head(const DevOcp *__restrict__ op,
       }
     }
     flag = what;
+    if ((mode & 1) && !(mode & 4)) count_carriable(S, n_done);
     arrive_and_publish(n_done, hw);  // (the host wants the finished count; the trial iterate below is for the next kernel of the stream)
   }
   __syncthreads();
@@ -1138,7 +1159,7 @@ __global__ void __launch_bounds__(128) k_sqp_accept(const DevOcp *__restrict__ o
   }
   double pc = 0.0, pg = 0.0, pv = 0.0;
   for (int t = tid; t <= T; t += blockDim.x) {
-    const double *qt = qts + ((long long)b * (T + 1) + t) * Q::SIZE;
+    const double *qt = qts + ((long long)b * (T + 1) + tile_slot(o, t)) * Q::SIZE;
     pc += qt[Q::cost];
     double g = 0.0;
 #pragma unroll
@@ -1176,6 +1197,7 @@ __global__ void __launch_bounds__(128) k_sqp_accept(const DevOcp *__restrict__ o
       sqp_iteration_end(S, false, alpha, iter, max_iter, n_done);
     }
     flag = what;
+    count_carriable(S, n_done);
     arrive_and_publish(n_done, hw);  // (counters only: the iterate below is consumed by later kernels of the stream)
   }
   __syncthreads();
@@ -1193,21 +1215,24 @@ __global__ void __launch_bounds__(128) k_sqp_accept(const DevOcp *__restrict__ o
 // ---------------------------------------------------------------------------
 __global__ void k_reset_state(DevState *st, int B, int *n_done) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b == 0) *n_done = 0;
+  if (b == 0) { n_done[0] = 0; n_done[6] = 0; }
   if (b >= B) return;
   DevState s;
   s.rho_sparse = st[b].rho_sparse; s.con = 0.0; s.admm_conv = 0; s.admm_iter = 0; s.ls_acc = 0; s.admm_refactor = 1;
   s.kkt = 0.0; s.cost = 0.0; s.merit = 0.0; s.gap = 0.0;
   s.preg = kRegMin; s.dreg = kRegMin;
   s.iter = 0; s.qp_iters = 0; s.solved = 0; s.flags = 0; s.done = 0; s.gains_iter = -1; s.dir_iter = -1; s.dir_fail = 0;
-  s.searching = 0; s.ls_n = 0; s.tiles_ok = 0; s.pad_ls = 0; s.preg_trial = kRegMin;
+  s.searching = 0; s.ls_n = 0; s.tiles_ok = 0; s.carry = 0; s.carry_counted = 0; s.pad_cc = 0; s.preg_trial = kRegMin;
   s.gains_preg = kRegMin; s.gains_dreg = kRegMin;
   st[b] = s;
 }
 
-// three words under one stamp: finished instances, line-search trials handed on, iterations ended with stale tiles
+// four words under one stamp: finished instances, line-search trials handed on, iterations ended with stale tiles, instances
+// whose tiles the next MPC step may inherit
 __global__ void k_publish3(const int *__restrict__ d_counts, unsigned long long *host_done, unsigned long long *host_handed,
-                           unsigned long long *host_stale, unsigned long long *host_seq, unsigned long long seq) {
+                           unsigned long long *host_stale, unsigned long long *host_carry, unsigned long long *host_seq,
+                           unsigned long long seq) {
+  __hip_atomic_store(host_carry, (unsigned long long)(unsigned)d_counts[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(host_done, (unsigned long long)(unsigned)d_counts[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(host_handed, (unsigned long long)(unsigned)d_counts[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(host_stale, (unsigned long long)(unsigned)d_counts[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1328,7 +1353,8 @@ template <int NV, bool CHAIN>
 __global__ void __launch_bounds__(128) k_mpc_prologue(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                       const double *__restrict__ dts, double *__restrict__ xs,
                                                       double *__restrict__ us, double *__restrict__ x0s,
-                                                      DevState *__restrict__ st, int *__restrict__ n_done, int from_pred) {
+                                                      DevState *__restrict__ st, int *__restrict__ n_done, int from_pred,
+                                                      int carry, int head, int *__restrict__ head_out) {
   constexpr int NX = 2 * NV, NU = NV, ND = NX + NU;
   extern __shared__ double sh_nodes[];  // [T][NX + NU]
   const DevModel &m = *mp;
@@ -1373,13 +1399,16 @@ AGX_UNROLL_NV
     X[tid] = x1;
   }
   if (tid == 0) {
-    if (b == 0) *n_done = 0;
+    if (b == 0) { n_done[0] = 0; n_done[6] = 0; *head_out = head; }  // (DevOcp::head: no kernel of this launch reads it)
     DevState s;
+    // tile carry (host: this step follows the previous one by one sample, see agx_ocp_mpc_step): the tiles the previous solve
+    // left belong to its final iterate and carry the regularisation this solve starts with
+    s.carry = (carry && st[b].tiles_ok && st[b].preg == kRegMin) ? 1 : 0;
     s.rho_sparse = st[b].rho_sparse; s.con = 0.0; s.admm_conv = 0; s.admm_iter = 0; s.ls_acc = 0; s.admm_refactor = 1;
     s.kkt = 0.0; s.cost = 0.0; s.merit = 0.0; s.gap = 0.0;
     s.preg = kRegMin; s.dreg = kRegMin;
     s.iter = 0; s.qp_iters = 0; s.solved = 0; s.flags = 0; s.done = 0; s.gains_iter = -1; s.dir_iter = -1; s.dir_fail = 0;
-  s.searching = 0; s.ls_n = 0; s.tiles_ok = 0; s.pad_ls = 0; s.preg_trial = kRegMin;
+    s.searching = 0; s.ls_n = 0; s.tiles_ok = 0; s.carry_counted = 0; s.pad_cc = 0; s.preg_trial = kRegMin;
     s.gains_preg = kRegMin; s.gains_dreg = kRegMin;
     st[b] = s;
   }

@@ -168,7 +168,8 @@ __device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *__res
   __shared__ double s_dt[kMaxHorizon];
   stage_dts(s_dt, dts, T);
   auto load_tile = [&](Tile &z, int t) {
-    const double *tl = qb + (long long)t * TS;
+    const int sl = tile_slot(o, t);  // wave-uniform: scalar registers
+    const double *tl = qb + (long long)sl * TS;
 #pragma unroll
     for (int r = 0; r < 4; ++r) z.hxx[r] = tl[oHxx[r]];
 #pragma unroll
@@ -177,7 +178,7 @@ __device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *__res
 #pragma unroll
       for (int r = 0; r < 4; ++r) z.fb[r] = tl[oF[r]];
     } else {
-      const double *al = ab + (long long)t * A::SIZE;
+      const double *al = ab + (long long)sl * A::SIZE;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         z.tx[s] = al[oTx[s]];
@@ -331,7 +332,7 @@ __device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *__res
     }
   }
   if (GAINS || !forward) return;
-  riccati_forward<NV>(b, T, dts, qb, Kws + (long long)b * T * NV * NX, kws + (long long)b * T * NV, dxs, wss, s_dt);
+  riccati_forward<NV>(o, b, T, dts, qb, Kws + (long long)b * T * NV * NX, kws + (long long)b * T * NV, dxs, wss, s_dt);
 }
 
 template <int NV, bool GAINS>

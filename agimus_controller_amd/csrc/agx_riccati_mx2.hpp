@@ -137,7 +137,8 @@ __device__ __forceinline__ void riccati_mx_seg(const int b, const DevOcp *__rest
   __shared__ double s_dt[kMaxHorizon];
   stage_dts(s_dt, dts, T);
   auto load_tile = [&](Tile &z, int t) {
-    const double *tl = qb + (long long)t * TS;
+    const int sl = tile_slot(o, t);  // wave-uniform: scalar registers
+    const double *tl = qb + (long long)sl * TS;
 #pragma unroll
     for (int r = 0; r < 4; ++r) z.hxx[r] = tl[oHxx[r]];
 #pragma unroll
@@ -146,7 +147,7 @@ __device__ __forceinline__ void riccati_mx_seg(const int b, const DevOcp *__rest
 #pragma unroll
       for (int r = 0; r < 4; ++r) z.fb[r] = tl[oF[r]];
     } else {
-      const double *al = ab + (long long)t * A::SIZE;
+      const double *al = ab + (long long)sl * A::SIZE;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         z.tx[s] = al[oTx[s]];
@@ -546,8 +547,9 @@ __global__ void __launch_bounds__(64, 2) k_riccati_mx2_fwd(const DevOcp *__restr
     g.kq = kr[cc];
     g.kv = kr[NV + cc];
     g.kw = kw[(long long)t * NV + rr];
-    g.fq = qb[(long long)t * TS + Q::f + rr];
-    g.fv = qb[(long long)t * TS + Q::f + NV + rr];
+    const double *tl = qb + (long long)tile_slot(*op, t) * TS;
+    g.fq = tl[Q::f + rr];
+    g.fv = tl[Q::f + NV + rr];
   };
   const bool last_seg = s == S - 1;
   auto fstep = [&](Gain &g, int t) {
