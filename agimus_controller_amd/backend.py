@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "agx_traj_get_point", "agx_traj_warmstart_from_reference", "agx_ocp_mpc_step", "agx_ocp_qp_tiles", "agx_ocp_set_quorum",
     "agx_traj_cartesian_sine_create", "agx_ocp_set_refs_async", "agx_ocp_refs_activate", "agx_ocp_refs_wait", "agx_host_alloc", "agx_host_free",
     "agx_ocp_download_async", "agx_ocp_download_wait",
+    "agx_traj_generic_create_weighted", "agx_traj_cartesian_sine_wi_create", "agx_traj_get_tile",
 ]  # fmt: skip
 
 
@@ -432,6 +433,34 @@ class HipOcp:
                                                   _p(bc(w_q, (nv,))), _p(bc(w_qdot, (nv,))), _p(bc(w_effort, (nv,))), _p(bc(w_pose, (6,))),
                                                   int(frame)))
 
+    def generic_trajectory_weighted(self, q, dq, ddq, w_q, w_qdot, w_effort, w_pose, frame, pose=None, w_collision=None):
+        """Resident trajectory from samples q, dq, ddq [B][n_points][nv] with a weight schedule (GenericVisualServoingTrajectory
+        upstream; `schedule_arrays` of that class gives the three arrays): w_pose [n_points][6] pose weights, pose [n_points][12]
+        end-effector references instead of the forward kinematics of q, w_collision [n_points] item weight of the collision
+        rows.  The per-sample arrays broadcast over B."""
+        B, nv = self.B, self.nv
+        q, dq, ddq = (_f8(a).reshape(B, -1, nv) for a in (q, dq, ddq))
+        assert q.shape == dq.shape == ddq.shape
+        n = q.shape[1]
+        bc = lambda a, shape: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape))  # noqa: E731
+        _chk(lib().agx_traj_generic_create_weighted(self._h, int(n), _p(q), _p(dq), _p(ddq), _p(bc(w_q, (nv,))), _p(bc(w_qdot, (nv,))),
+                                                    _p(bc(w_effort, (nv,))), int(frame), _p(bc(pose, (B, n, 12))), _p(bc(w_pose, (B, n, 6))),
+                                                    _p(bc(w_collision, (B, n)))))
+
+    def cartesian_sine_weight_increasing_trajectory(self, n_points, dt, q0, amp, pulsation, period, w_increasing, w_q, w_qdot, w_effort,
+                                                    w_pose, frame, scale_duration=0.2, precision=1e-5, it_max=10000):
+        """Resident trajectory of SinusWaveCartesianSpaceWeightIncreasing upstream: the joints follow the Cartesian sine, the
+        end-effector target switches between its extrema and the translational pose weight ramps over every half cycle.
+        q0 [B][nv], amp / pulsation / period [B][3]; `w_increasing`: a trajectories.weight_increasing.WeightIncreasing; the last
+        three entries of w_pose are the rotational weights."""
+        B, nv = self.B, self.nv
+        bc = lambda a, shape: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape))  # noqa: E731
+        rate = float(np.arctanh(w_increasing.percent) / w_increasing.time_reach_percent)
+        _chk(lib().agx_traj_cartesian_sine_wi_create(self._h, int(n_points), C.c_double(dt), _p(bc(q0, (B, nv))), _p(bc(amp, (B, 3))),
+                                                     _p(bc(pulsation, (B, 3))), C.c_double(scale_duration), C.c_double(precision), int(it_max),
+                                                     _p(bc(w_q, (nv,))), _p(bc(w_qdot, (nv,))), _p(bc(w_effort, (nv,))), _p(bc(w_pose, (6,))),
+                                                     int(frame), _p(bc(period, (B, 3))), C.c_double(w_increasing.max_weight), C.c_double(rate)))
+
     def set_horizon_indexes(self, idx):
         """TrajectoryBuffer.horizon_indexes for the resident trajectory (None = uniform)."""
         a = None if idx is None else np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(self.T + 1))
@@ -446,6 +475,13 @@ class HipOcp:
         pose = np.empty((B, 12))
         _chk(lib().agx_traj_get_point(self._h, int(k), _p(q), _p(v), _p(a), _p(u), _p(pose)))
         return q, v, a, u, pose
+
+    def traj_tile(self, k: int, terminal: bool = False):
+        """Reference tile [B][stride] of resident sample k in the running or the terminal layout (`PackedOcp.row_view` offsets).
+        A debug reader: it ends the tile carry."""
+        out = np.empty((self.B, self.stride))
+        _chk(lib().agx_traj_get_tile(self._h, int(k), 1 if terminal else 0, _p(out)))
+        return out
 
     def warmstart_from_reference(self):
         _chk(lib().agx_traj_warmstart_from_reference(self._h))

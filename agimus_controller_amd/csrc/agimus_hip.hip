@@ -2176,30 +2176,49 @@ int agx_traj_sine_create(agx_ocp *o, int n_points, double dt, const double *q0, 
   return agx_traj_set_window(o, 0);
 }
 
-int agx_traj_generic_create(agx_ocp *o, int n_points, const double *q, const double *dq, const double *ddq, const double *w_q,
-                            const double *w_qdot, const double *w_effort, const double *w_pose, int frame) {
-  if (!o || !q || !dq || !ddq || !w_q || !w_qdot || !w_effort || !w_pose) return fail("agx_traj_generic_create: null argument");
-  if (n_points < o->T + 1) return fail("agx_traj_generic_create: trajectory shorter than the horizon");
-  if (frame < 0 || frame >= o->hm.nframes) return fail("agx_traj_generic_create: frame id out of range");
+// The caller-fed resident trajectory behind agx_traj_generic_create / agx_traj_generic_create_weighted (`fn`: the entry point, for
+// the messages).  pose / gw_pose / gw_item: optional per-sample arrays [B][n_points][12] / [6] / [1] (host); w_pose: the constant
+// pose weights used without gw_pose.
+static int traj_generic_build(agx_ocp *o, const char *fn, int n_points, const double *q, const double *dq, const double *ddq,
+                              const double *w_q, const double *w_qdot, const double *w_effort, const double *w_pose, int frame,
+                              const double *pose, const double *gw_pose, const double *gw_item) {
+  const std::string name(fn);
+  if (n_points < o->T + 1) return fail(name + ": trajectory shorter than the horizon");
+  if (frame < 0 || frame >= o->hm.nframes) return fail(name + ": frame id out of range");
   if (set_device(o)) return -1;
   if (carry_invalidate(o)) return -1;
-  const size_t B = o->B, nv = o->nv, n = B * (size_t)n_points * nv;
+  const size_t B = o->B, nv = o->nv, np = B * (size_t)n_points, n = np * nv;
   if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
   if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
   if (o->d_sine) { (void)hipFree(o->d_sine); o->d_sine = nullptr; }
   HIPCHK(hipMalloc((void **)&o->d_traj, sizeof(double) * B * n_points * 2 * o->stride));
   HIPCHK(hipMalloc((void **)&o->d_pts, sizeof(double) * B * n_points * (4 * nv + 12)));
-  HIPCHK(hipMalloc((void **)&o->d_sine, sizeof(double) * 3 * n));
+  // q | dq | ddq samples, then the optional per-sample poses, pose weights and collision item weights
+  HIPCHK(hipMalloc((void **)&o->d_sine, sizeof(double) * (3 * n + (pose ? 12 * np : 0) + (gw_pose ? 6 * np : 0) + (gw_item ? np : 0))));
   double *d = o->d_sine;
-  if (up(o, d, q, B * (size_t)n_points, 1) || up(o, d + n, dq, B * (size_t)n_points, 1) || up(o, d + 2 * n, ddq, B * (size_t)n_points, 1)) return -1;
+  if (up(o, d, q, np, 1) || up(o, d + n, dq, np, 1) || up(o, d + 2 * n, ddq, np, 1)) return -1;
   agx::SineParams sp;
   std::memset(&sp, 0, sizeof(sp));
   sp.gq = d; sp.gdq = d + n; sp.gddq = d + 2 * n;
+  double *extra = d + 3 * n;
+  if (pose) {
+    HIPCHK(hipMemcpyAsync(extra, pose, sizeof(double) * 12 * np, hipMemcpyHostToDevice, o->stream));
+    sp.gpose = extra; extra += 12 * np;
+  }
+  if (gw_pose) {
+    HIPCHK(hipMemcpyAsync(extra, gw_pose, sizeof(double) * 6 * np, hipMemcpyHostToDevice, o->stream));
+    sp.gw_pose = extra; extra += 6 * np;
+  }
+  if (gw_item) {
+    HIPCHK(hipMemcpyAsync(extra, gw_item, sizeof(double) * np, hipMemcpyHostToDevice, o->stream));
+    sp.gw_item = extra;
+  }
   for (size_t i = 0; i < nv; ++i) {  // pad joints: weight 1 on an identically zero residual
     const bool real = i < (size_t)o->nvu;
     sp.w_q[i] = real ? w_q[i] : 1.0; sp.w_qdot[i] = real ? w_qdot[i] : 1.0; sp.w_effort[i] = real ? w_effort[i] : 1.0;
   }
-  for (int i = 0; i < 6; ++i) sp.w_pose[i] = w_pose[i];
+  if (w_pose)
+    for (int i = 0; i < 6; ++i) sp.w_pose[i] = w_pose[i];
   sp.dt = 0.0; sp.n_points = n_points; sp.frame = frame;
   o->n_points = n_points;
   int rc = dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
@@ -2216,14 +2235,35 @@ int agx_traj_generic_create(agx_ocp *o, int n_points, const double *q, const dou
   return agx_traj_set_window(o, 0);
 }
 
-int agx_traj_cartesian_sine_create(agx_ocp *o, int n_points, double dt, const double *q0, const double *amp, const double *pulsation,
-                                   double scale_duration, double precision, int it_max, const double *w_q, const double *w_qdot,
-                                   const double *w_effort, const double *w_pose, int frame) {
-  if (!o || !q0 || !amp || !pulsation || !w_q || !w_qdot || !w_effort || !w_pose) return fail("agx_traj_cartesian_sine_create: null argument");
-  if (n_points < o->T + 1) return fail("agx_traj_cartesian_sine_create: trajectory shorter than the horizon");
-  if (frame < 0 || frame >= o->hm.nframes) return fail("agx_traj_cartesian_sine_create: frame id out of range");
-  if (!(scale_duration > 0.0) || !(precision > 0.0) || it_max < 1) return fail("agx_traj_cartesian_sine_create: scale_duration, precision, it_max must be positive");
-  if (o->nv > 7) return fail("agx_traj_cartesian_sine_create: nv <= 7");
+int agx_traj_generic_create(agx_ocp *o, int n_points, const double *q, const double *dq, const double *ddq, const double *w_q,
+                            const double *w_qdot, const double *w_effort, const double *w_pose, int frame) {
+  if (!o || !q || !dq || !ddq || !w_q || !w_qdot || !w_effort || !w_pose) return fail("agx_traj_generic_create: null argument");
+  return traj_generic_build(o, "agx_traj_generic_create", n_points, q, dq, ddq, w_q, w_qdot, w_effort, w_pose, frame, nullptr, nullptr, nullptr);
+}
+
+int agx_traj_generic_create_weighted(agx_ocp *o, int n_points, const double *q, const double *dq, const double *ddq, const double *w_q,
+                                     const double *w_qdot, const double *w_effort, int frame, const double *pose, const double *w_pose,
+                                     const double *w_collision) {
+  if (!o || !q || !dq || !ddq || !w_q || !w_qdot || !w_effort || !w_pose) return fail("agx_traj_generic_create_weighted: null argument");
+  return traj_generic_build(o, "agx_traj_generic_create_weighted", n_points, q, dq, ddq, w_q, w_qdot, w_effort, nullptr, frame, pose, w_pose,
+                            w_collision);
+}
+
+// The Cartesian sine generators: `period` null = agx_traj_cartesian_sine_create, set = the weight-increasing variant (`fn`: the entry
+// point, for the messages).
+static int traj_cartesian_build(agx_ocp *o, const char *fn, int n_points, double dt, const double *q0, const double *amp, const double *pulsation,
+                                double scale_duration, double precision, int it_max, const double *w_q, const double *w_qdot,
+                                const double *w_effort, const double *w_pose, int frame, const double *period, double max_weight, double rate) {
+  const std::string name(fn);
+  if (n_points < o->T + 1) return fail(name + ": trajectory shorter than the horizon");
+  if (frame < 0 || frame >= o->hm.nframes) return fail(name + ": frame id out of range");
+  if (!(scale_duration > 0.0) || !(precision > 0.0) || it_max < 1) return fail(name + ": scale_duration, precision, it_max must be positive");
+  if (o->nv > 7) return fail(name + ": nv <= 7");
+  if (period) {
+    for (size_t i = 0; i < (size_t)o->B * 3; ++i)
+      if (!(period[i] > 0.0) || !std::isfinite(period[i])) return fail(name + ": periods must be positive");
+    if (!std::isfinite(max_weight) || !std::isfinite(rate)) return fail(name + ": max_weight and rate must be finite");
+  }
   if (set_device(o)) return -1;
   if (carry_invalidate(o)) return -1;
   const size_t B = o->B, nv = o->nv, n = B * (size_t)n_points * nv;
@@ -2232,21 +2272,28 @@ int agx_traj_cartesian_sine_create(agx_ocp *o, int n_points, double dt, const do
   if (o->d_sine) { (void)hipFree(o->d_sine); o->d_sine = nullptr; }
   HIPCHK(hipMalloc((void **)&o->d_traj, sizeof(double) * B * n_points * 2 * o->stride));
   HIPCHK(hipMalloc((void **)&o->d_pts, sizeof(double) * B * n_points * (4 * nv + 12)));
-  // q | dq | ddq samples, then the per-instance parameters q0 | amp | pulsation and the failure flags
-  const size_t npar = B * (nv + 6), npose = B * (size_t)n_points * 12;
+  // q | dq | ddq samples, then the per-instance parameters q0 | amp | pulsation | period, the poses, the scheduled pose weights
+  // (weight-increasing variant) and the failure flags
+  const size_t npar = B * (nv + 9), npose = B * (size_t)n_points * 12, nw = period ? B * (size_t)n_points * 6 : 0;
   o->n_points = 0;  // until the trajectory is complete: a failed build leaves nothing a later window / MPC step could consume
-  HIPCHK(hipMalloc((void **)&o->d_sine, sizeof(double) * (3 * n + npar + npose) + sizeof(int) * B));
-  double *d = o->d_sine, *dpar = d + 3 * n, *dpose = dpar + npar;
-  int *dfail = reinterpret_cast<int *>(dpose + npose);
+  HIPCHK(hipMalloc((void **)&o->d_sine, sizeof(double) * (3 * n + npar + npose + nw) + sizeof(int) * B));
+  double *d = o->d_sine, *dpar = d + 3 * n, *dpose = dpar + npar, *dw = dpose + npose;
+  int *dfail = reinterpret_cast<int *>(dw + nw);
   HIPCHK(hipMemsetAsync(d + 2 * n, 0, sizeof(double) * n, o->stream));  // ddq = 0
   if (up(o, dpar, q0, B, 1)) return -1;
   HIPCHK(hipMemcpyAsync(dpar + B * nv, amp, sizeof(double) * B * 3, hipMemcpyHostToDevice, o->stream));
   HIPCHK(hipMemcpyAsync(dpar + B * nv + B * 3, pulsation, sizeof(double) * B * 3, hipMemcpyHostToDevice, o->stream));
+  if (period) HIPCHK(hipMemcpyAsync(dpar + B * nv + B * 6, period, sizeof(double) * B * 3, hipMemcpyHostToDevice, o->stream));
   agx::CartSineParams cp;
+  std::memset(&cp, 0, sizeof(cp));
   cp.q0 = dpar; cp.amp = dpar + B * nv; cp.puls = dpar + B * nv + B * 3;
   cp.dt = dt; cp.scale = scale_duration; cp.precision = precision;
   cp.n_points = n_points; cp.frame = frame; cp.it_max = it_max;
   cp.q = d; cp.dq = d + n; cp.pose = dpose; cp.fail = dfail;
+  if (period) {
+    cp.period = dpar + B * nv + B * 6; cp.max_weight = max_weight; cp.rate = rate; cp.wpose = dw;
+    for (int i = 0; i < 3; ++i) cp.w_rot[i] = w_pose[3 + i];
+  }
   agx::SineParams sp;
   std::memset(&sp, 0, sizeof(sp));
   sp.gq = d; sp.gdq = d + n; sp.gddq = d + 2 * n;
@@ -2257,11 +2304,13 @@ int agx_traj_cartesian_sine_create(agx_ocp *o, int n_points, double dt, const do
   for (int i = 0; i < 6; ++i) sp.w_pose[i] = w_pose[i];
   sp.dt = 0.0; sp.n_points = n_points; sp.frame = frame;
   sp.gpose = dpose;
+  if (period) sp.gw_pose = dw;
   int rc = dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
     if constexpr (NV <= 7) {
-      hipLaunchKernelGGL((agx::k_cartesian_sine_ik<NV, CH>), dim3((int)((B + 63) / 64)), dim3(64), 0, o->stream, o->d_model, (int)B, cp);
+      if (period) hipLaunchKernelGGL((agx::k_cartesian_sine_ik<NV, CH, true>), dim3((int)((B + 63) / 64)), dim3(64), 0, o->stream, o->d_model, (int)B, cp);
+      else hipLaunchKernelGGL((agx::k_cartesian_sine_ik<NV, CH>), dim3((int)((B + 63) / 64)), dim3(64), 0, o->stream, o->d_model, (int)B, cp);
       const long long units = (long long)B * n_points;
       hipLaunchKernelGGL((agx::k_sine_fill<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, sp, o->d_traj, o->d_pts);
     }
@@ -2285,6 +2334,24 @@ int agx_traj_cartesian_sine_create(agx_ocp *o, int n_points, double dt, const do
   o->n_points = n_points;
   if (traj_frames(o, frame)) return -1;
   return agx_traj_set_window(o, 0);
+}
+
+int agx_traj_cartesian_sine_create(agx_ocp *o, int n_points, double dt, const double *q0, const double *amp, const double *pulsation,
+                                   double scale_duration, double precision, int it_max, const double *w_q, const double *w_qdot,
+                                   const double *w_effort, const double *w_pose, int frame) {
+  if (!o || !q0 || !amp || !pulsation || !w_q || !w_qdot || !w_effort || !w_pose) return fail("agx_traj_cartesian_sine_create: null argument");
+  return traj_cartesian_build(o, "agx_traj_cartesian_sine_create", n_points, dt, q0, amp, pulsation, scale_duration, precision, it_max, w_q, w_qdot,
+                              w_effort, w_pose, frame, nullptr, 0.0, 0.0);
+}
+
+int agx_traj_cartesian_sine_wi_create(agx_ocp *o, int n_points, double dt, const double *q0, const double *amp, const double *pulsation,
+                                      double scale_duration, double precision, int it_max, const double *w_q, const double *w_qdot,
+                                      const double *w_effort, const double *w_pose, int frame, const double *period, double max_weight,
+                                      double rate) {
+  if (!o || !q0 || !amp || !pulsation || !w_q || !w_qdot || !w_effort || !w_pose || !period)
+    return fail("agx_traj_cartesian_sine_wi_create: null argument");
+  return traj_cartesian_build(o, "agx_traj_cartesian_sine_wi_create", n_points, dt, q0, amp, pulsation, scale_duration, precision, it_max, w_q,
+                              w_qdot, w_effort, w_pose, frame, period, max_weight, rate);
 }
 
 int agx_traj_set_horizon_indexes(agx_ocp *o, const int32_t *idx) {
@@ -2349,6 +2416,30 @@ int agx_traj_get_point(agx_ocp *o, int k, double *q, double *v, double *a, doubl
     if (u) std::memcpy(u + b * nvu, p + 3 * nv, sizeof(double) * nvu);
     if (pose) std::memcpy(pose + b * 12, p + 4 * nv, sizeof(double) * 12);
   }
+  return 0;
+}
+
+int agx_traj_get_tile(agx_ocp *o, int k, int terminal, double *out) {
+  if (!o || !out) return fail("agx_traj_get_tile: null argument");
+  if (!o->d_traj) return fail("agx_traj_get_tile: no resident trajectory");
+  if (k < 0 || k >= o->n_points) return fail("agx_traj_get_tile: sample out of range");
+  if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
+  const size_t B = o->B, st = o->stride, su = o->stride_u;
+  const int lay = terminal ? 1 : 0;
+  std::vector<double> h(B * st);
+  HIPCHK(hipMemcpy2DAsync(h.data(), sizeof(double) * st, o->d_traj + ((size_t)k * 2 + lay) * st, sizeof(double) * o->n_points * 2 * st,
+                          sizeof(double) * st, B, hipMemcpyDeviceToHost, o->stream));
+  HIPCHK(hipStreamSynchronize(o->stream));
+  // the generators write the rows of the layout; what lies behind them in a slot of `stride` doubles is returned as zeros
+  const DevRows &R = o->ho.rows[lay];
+  const size_t used = R.n ? (size_t)R.off[R.n - 1] + 1 + R.nref[R.n - 1] + R.nr[R.n - 1] : 0;
+  std::memset(out, 0, sizeof(double) * B * su);
+  for (size_t b = 0; b < B; ++b)
+    for (size_t e = 0; e < used; ++e) {
+      const int eu = o->padded ? o->refmap[lay][e] : (int)e;  // pad joints have no place in the caller's tile
+      if (eu >= 0) out[b * su + eu] = h[b * st + e];
+    }
   return 0;
 }
 

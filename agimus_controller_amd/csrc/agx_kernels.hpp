@@ -1576,7 +1576,26 @@ struct CartSineParams {
   double *q, *dq;                 // [B][n_points][nv]
   double *pose;                   // [B][n_points][12]: the DESIRED end-effector pose (R row major | p), the reference the points carry
   int *fail;                      // [B]
+  // weight-increasing variant (k_cartesian_sine_ik<.., true>): the inverse kinematics still follows the sine, `pose` receives the
+  // switching target and `wpose` the scheduled pose weights of every sample
+  const double *period;           // [B][3] cycle duration per axis
+  double max_weight, rate;        // translational weight  max_weight tanh(rate t)
+  double w_rot[3];                // rotational weights (constant)
+  double *wpose;                  // [B][n_points][6]
 };
+// SinusWaveCartesianSpaceWeightIncreasing.get_targets_time (trajectories/sine_wave_cartesian_space_weight_increasing.py:51-61
+// upstream): time since the start of the running cycle and the same time half a cycle away.  Which of the two is the smaller one
+// decides the extremum the target sits at, so quotient, truncation and remainder are the host class's operations in its order,
+// each rounded on its own (no fused multiply-add): a sample on a half-cycle boundary takes the same side on host and device.
+AGX_DEV void cycle_target_times(double t, double cd, double *t1, double *t2) {
+#pragma clang fp contract(off)
+  const double cycle_start = trunc(t / cd) * cd;
+  double a = t - cycle_start;
+  if (a > cd) a = a - cd;
+  const double half = cd / 2.0;
+  *t1 = a;
+  *t2 = a < half ? a + half : a - half;
+}
 // x <- A^-1 x for a symmetric positive definite 6 x 6 (J J'): elimination without pivoting
 AGX_DEV void solve_spd6(double *A, double *x) {
 #pragma unroll
@@ -1622,7 +1641,7 @@ AGX_UNROLL_NV
     y[c] = s;
   }
 }
-template <int NV, bool CHAIN>
+template <int NV, bool CHAIN, bool WI = false>
 __global__ void __launch_bounds__(64) k_cartesian_sine_ik(const DevModel *__restrict__ mp, int B, CartSineParams cp) {
   const DevModel &m = *mp;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1678,8 +1697,22 @@ AGX_UNROLL_NV
     double *po = cp.pose + ((long long)b * cp.n_points + i) * 12;
 #pragma unroll
     for (int e = 0; e < 9; ++e) po[e] = R0[e];
+    if constexpr (!WI) {
 #pragma unroll
-    for (int e = 0; e < 3; ++e) po[9 + e] = des_p[e];
+      for (int e = 0; e < 3; ++e) po[9 + e] = des_p[e];
+    } else {
+      // sine_wave_cartesian_space_weight_increasing.py:75-88 upstream: the target of an axis is the extremum p0 +- A s(t) the sine
+      // is heading for, and the weight of that axis grows with the time spent in the running half cycle
+      double *wo = cp.wpose + ((long long)b * cp.n_points + i) * 6;
+#pragma unroll
+      for (int e = 0; e < 3; ++e) {
+        double t1, t2;
+        cycle_target_times(t, cp.period[3 * b + e], &t1, &t2);
+        po[9 + e] = t1 < t2 ? p0[e] + amp[e] * quint : p0[e] - amp[e] * quint;
+        wo[e] = cp.max_weight * tanh(fmax(t1, t2) * cp.rate);
+        wo[3 + e] = cp.w_rot[e];
+      }
+    }
   }
   cp.fail[b] = failed;
 }
@@ -1779,6 +1812,9 @@ struct SineParams {
   // [B][n_points][nv] each; when set they replace the sine formula
   const double *gq, *gdq, *gddq;
   const double *gpose;  // optional [B][n_points][12]: end-effector reference of every sample (otherwise the pose of the sample's q)
+  // weight schedules (what OCPCrocoGeneric._update_node takes from w_end_effector_poses / w_collision_avoidance of every point)
+  const double *gw_pose;  // optional [B][n_points][6]: activation weights of the frame placement / translation / rotation rows
+  const double *gw_item;  // optional [B][n_points]: item weight of the collision-distance rows
   double w_q[AGX_MAX_NV], w_qdot[AGX_MAX_NV], w_effort[AGX_MAX_NV], w_pose[6];
   double dt;
   int n_points, frame;
@@ -1792,7 +1828,7 @@ __global__ void k_sine_fill(const DevModel *__restrict__ mp, const DevOcp *__res
   const long long unit = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (unit >= (long long)o.B * sp.n_points) return;
   const int b = (int)(unit / sp.n_points), kk = (int)(unit % sp.n_points);
-  const double t = sp.t0[b] + kk * sp.dt;
+  const double t = sp.gq ? 0.0 : sp.t0[b] + kk * sp.dt;  // caller-given samples carry no time (and no t0 array)
   double q[NV], dq[NV], ddq[NV], u[NV];
   if (sp.gq) {
 AGX_UNROLL_NV
@@ -1835,6 +1871,9 @@ AGX_UNROLL_NV
   for (int e = 0; e < 9; ++e) pt[4 * NV + e] = RF[e];
 AGX_UNROLL_NV
   for (int e = 0; e < 3; ++e) pt[4 * NV + 9 + e] = pF[e];
+  double wp[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) wp[e] = sp.gw_pose ? sp.gw_pose[unit * 6 + e] : sp.w_pose[e];
   for (int layout = 0; layout < 2; ++layout) {
     const DevRows &rows = o.rows[layout];
     double *tile = traj + unit * 2 * o.stride + layout * o.stride;
@@ -1850,13 +1889,14 @@ AGX_UNROLL_NV
       } else if (kind == AGX_RES_FRAME_PLACEMENT) {
         for (int e = 0; e < 9; ++e) rr[e] = RF[e];
         for (int e = 0; e < 3; ++e) rr[9 + e] = pF[e];
-        for (int e = 0; e < 6; ++e) aw[e] = sp.w_pose[e];
+        for (int e = 0; e < 6; ++e) aw[e] = wp[e];
       } else if (kind == AGX_RES_FRAME_TRANSLATION) {
-        for (int e = 0; e < 3; ++e) { rr[e] = pF[e]; aw[e] = sp.w_pose[e]; }
+        for (int e = 0; e < 3; ++e) { rr[e] = pF[e]; aw[e] = wp[e]; }
       } else if (kind == AGX_RES_FRAME_ROTATION) {
         for (int e = 0; e < 9; ++e) rr[e] = RF[e];
-        for (int e = 0; e < 3; ++e) aw[e] = sp.w_pose[3 + e];
+        for (int e = 0; e < 3; ++e) aw[e] = wp[3 + e];
       } else {
+        if (kind == AGX_RES_COLLISION && sp.gw_item) tr[0] = sp.gw_item[unit];
         for (int e = 0; e < rows.nref[r] + rows.nr[r]; ++e) rr[e] = 0.0;
       }
     }

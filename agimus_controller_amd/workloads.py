@@ -304,5 +304,33 @@ def cartesian_sine_batch_params(B: int, seed0: int = 1234, lower=None, upper=Non
     return q0, amp, puls
 
 
+def weight_increasing_schedule(n_points: int, dt: float, p0, amp_xyz, period, max_weight: float, rate: float, w_rot=(0.0, 0.0, 0.0),
+                               scale_duration=0.2):
+    """Closed form of the SinusWaveCartesianSpaceWeightIncreasing schedule
+    (trajectories/sine_wave_cartesian_space_weight_increasing.py:51-88 upstream) for B instances at the sample times k dt:
+    (target [B][n_points][3], w_pose [B][n_points][6]).  Per axis the target is  p0 + A s(t)  while the time t1 since the cycle began
+    is below half the cycle duration and  p0 - A s(t)  afterwards; its weight is  max_weight tanh(rate max(t1, t2))  with
+    t2 = t1 +- period / 2 (rate = arctanh(percent) / time_reach_percent of a WeightIncreasing).  p0, amp_xyz, period: [B][3].
+    The cycle arithmetic is the class's, operation by operation, so boundary samples fall on the same side."""
+    p0 = np.asarray(p0, dtype=float)
+    B = p0.shape[0]
+    amp = np.broadcast_to(np.asarray(amp_xyz, dtype=float), (B, 3))[:, None, :]
+    cd = np.broadcast_to(np.asarray(period, dtype=float), (B, 3))[:, None, :]
+    t = (np.arange(n_points) * dt)[None, :, None]
+    d = float(scale_duration)
+    s = np.clip(t / d, 0.0, 1.0)
+    quint = 10 * s**3 - 15 * s**4 + 6 * s**5
+    t1 = t - np.trunc(t / cd) * cd
+    t1 = np.where(t1 > cd, t1 - cd, t1)
+    half = cd / 2.0
+    first = t1 < half
+    t2 = np.where(first, t1 + half, t1 - half)
+    target = p0[:, None, :] + np.where(first, 1.0, -1.0) * (amp * quint)
+    w_pose = np.empty((B, n_points, 6))
+    w_pose[..., :3] = max_weight * np.tanh(np.maximum(t1, t2) * rate)
+    w_pose[..., 3:] = np.asarray(w_rot, dtype=float)
+    return target, w_pose
+
+
 # Weights of the reference's sine-wave test (tests/test_sin_wave_configuration_space.py:138-144).
 SINE_WEIGHTS = dict(w_q=1.0, w_qdot=0.1, w_effort=3e-4, w_pose=0.1)

@@ -340,6 +340,31 @@ int agx_traj_cartesian_sine_create(agx_ocp *ocp, int n_points, double dt, const 
                                    const double *pulsation, double scale_duration, double precision, int it_max,
                                    const double *w_q, const double *w_qdot, const double *w_effort, const double *w_pose,
                                    int frame);
+/* agx_traj_generic_create with a weight schedule: what the cost rows take from the weights of every point of a user-fed trajectory
+ * (ocp_croco_generic.py:203-210, :257-264, :311-318 w_end_effector_poses; :713-719 w_collision_avoidance), resident on the device.  GenericVisualServoingTrajectory
+ * (trajectories/generic_visual_servoing_trajectory.py:93-145) is the generator this serves: its pose weights ramp with
+ * WeightIncreasing (trajectories/weight_increasing.py:17-20) and its collision weight changes with the visual-servoing state.
+ *   pose        [B][n_points][12] or NULL: end-effector reference of every sample (R row major | p) instead of the forward
+ *               kinematics of its q (:97-100: the pose re-expressed in the object frame);
+ *   w_pose      [B][n_points][6]: activation weights of the frame placement / translation (first 3) / rotation (last 3) rows;
+ *   w_collision [B][n_points] or NULL: item weight of the collision-distance rows (NULL: the row's YAML weight).
+ * `frame` is the frame the rows look at; it need not be the frame whose poses are given (:57: the "_vs" frame).  Every model
+ * size agx_traj_generic_create serves.                                                                                  */
+int agx_traj_generic_create_weighted(agx_ocp *ocp, int n_points, const double *q, const double *dq, const double *ddq,
+                                     const double *w_q, const double *w_qdot, const double *w_effort, int frame,
+                                     const double *pose, const double *w_pose, const double *w_collision);
+/* agx_traj_cartesian_sine_create with the schedule of SinusWaveCartesianSpaceWeightIncreasing
+ * (trajectories/sine_wave_cartesian_space_weight_increasing.py:51-108): q, dq from the inverse kinematics of the sine as there; the
+ * end-effector reference of a point has the initial orientation and, per axis, the extremum p0 + amp s(t) or p0 - amp s(t) the sine is
+ * heading for (:51-61 get_targets_time with the cycle duration period[b][axis]: t1 = time since the cycle started, t2 = t1 +- period/2,
+ * plus while t1 < t2); the translational pose weight of that axis is max_weight tanh(rate max(t1, t2)) (weight_increasing.py:17-20
+ * with rate = arctanh(percent) / time_reach_percent).  w_pose [6]: its last three entries are the rotational weights, the first
+ * three are replaced by the schedule.  t / period, its truncation and the remainder are rounded one by one as on the host, so a
+ * sample on a half-cycle boundary takes the host's side.  period [B][3] > 0.  nv <= 7; failures as agx_traj_cartesian_sine_create. */
+int agx_traj_cartesian_sine_wi_create(agx_ocp *ocp, int n_points, double dt, const double *q0, const double *amp,
+                                      const double *pulsation, double scale_duration, double precision, int it_max,
+                                      const double *w_q, const double *w_qdot, const double *w_effort, const double *w_pose,
+                                      int frame, const double *period, double max_weight, double rate);
 /* Point the solver at the horizon window starting at sample `k0` of the
  * resident trajectory (TrajectoryBuffer.horizon, trajectory.py:218-222, with
  * uniform horizon indexes).                                                    */
@@ -350,6 +375,11 @@ int agx_traj_set_window(agx_ocp *ocp, int k0);
 int agx_traj_set_horizon_indexes(agx_ocp *ocp, const int32_t *idx);
 /* Copy trajectory sample k of every instance to the host: q,v,a,u [B][nv], pose [B][12]. */
 int agx_traj_get_point(agx_ocp *ocp, int k, double *q, double *v, double *a, double *u, double *pose);
+/* Copy the reference tile of sample k to the host, out [B][stride]: [item weight | reference | activation weights] of every row
+ * in the running (terminal = 0) or the terminal layout, what OCPCrocoGeneric.set_reference_weighted_trajectory
+ * (ocp_croco_generic.py:855-892) would have written for that point; doubles behind the last row are zero.  A debug reader:
+ * the next MPC step recomputes every derivative tile.                                       */
+int agx_traj_get_tile(agx_ocp *ocp, int k, int terminal, double *out);
 /* Warm start from the reference (WarmStartReference.generate,
  * warm_start_reference.py:33-96) on the device: xs <- [x0, ref[1:]], us <- ref efforts. */
 int agx_traj_warmstart_from_reference(agx_ocp *ocp);
