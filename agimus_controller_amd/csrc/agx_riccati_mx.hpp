@@ -21,11 +21,15 @@
 //
 // Same mathematics as riccati_body (agx_kernels.hpp) -- mim_solvers SolverCSQP backwardPass /
 // computeDirection as called from agimus_controller/ocp_base_croco.py:172; results agree to round-off.
+//
+// riccati_mx_seg is the one implementation of the sweep: the one-wave kernels of this file run it over the whole horizon,
+// the two-level kernels of agx_riccati_mx2.hpp over segments of it (with the extra recursions CLOOP / ELEM switch on).
 #pragma once
 
 namespace agx {
 
 typedef double mx4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) double lds_double;  // a double in LDS: a pointer to it is indexed with 32 bits
 
 // Nodes of tile elements in flight per wave (13 doubles per lane and node).  The sweep is bound by the
 // latency of its tile loads: 1024 waves x depth x 3 KB in flight over ~3 us of loaded latency is the
@@ -35,7 +39,6 @@ typedef double mx4 __attribute__((ext_vector_type(4)));
 #endif
 constexpr int kMxDepth = AGX_MX_DEPTH;
 
-
 // lane K of my 16-lane row (row_newbcast on the double-precision ALU, K compile time)
 template <int K>
 __device__ __forceinline__ double row_bcast(double x) { return __builtin_amdgcn_mov_dpp(x, 0x150 + K, 0xf, 0xf, false); }
@@ -43,23 +46,6 @@ __device__ __forceinline__ double row_bcast(double x) { return __builtin_amdgcn_
 __device__ __forceinline__ double row_ror8(double x) {
   const int lo = __double2loint(x), hi = __double2hiint(x);
   return __hiloint2double(__builtin_amdgcn_mov_dpp(hi, 0x128, 0xf, 0xf, false), __builtin_amdgcn_mov_dpp(lo, 0x128, 0xf, 0xf, false));
-}
-// Value of lane 16 G + (my column) for every lane: the 16 lanes of row group G broadcast to the four groups with gfx950's
-// v_permlane16_swap / v_permlane32_swap (VALU) instead of ds_bpermute through the LDS crossbar: swap(x, x) leaves
-// [x0 x0 x2 x2] / [x1 x1 x3 x3] (16-lane rows), the second swap copies the half that holds group G over the other one.
-// Tried for the pivot row of the elimination (7 fetches per node, -DAGX_MX_PERMLANE) and NOT used: four swaps per double, each
-// behind the two wait states the ISA wants after a VALU write of its operands, cost the chain more than the two
-// ds_bpermute pairs they replace, whose latency overlaps the reciprocal (measured: sweeps + 6 %, batch-1 step + 10 %).
-template <int G>
-__device__ __forceinline__ int bcast_group_b32(int x) {
-  const auto a = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-  const int y = (G & 1) ? a[1] : a[0];
-  const auto b = __builtin_amdgcn_permlane32_swap(y, y, false, false);
-  return (G & 2) ? b[1] : b[0];
-}
-template <int G>
-__device__ __forceinline__ double bcast_group(double x) {
-  return __hiloint2double(bcast_group_b32<G>(__double2hiint(x)), bcast_group_b32<G>(__double2loint(x)));
 }
 // 1 / x to full precision with a dependent chain of 1 + 3 operations instead of 1 + 4 (fast_rcp): with e = 1 - x y0,
 // y0 (1 + e)(1 + e^2) = y0 (1 + e + e^2 + e^3), e^2 formed next to the first correction.  The pivots are on the
@@ -72,26 +58,25 @@ __device__ __forceinline__ double chain_rcp(double x) {
 }
 __device__ __forceinline__ double flip_sign(double x) { return __hiloint2double(__double2hiint(x) ^ (int)0x80000000, __double2loint(x)); }
 
-template <int NV, bool GAINS>
-__device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *__restrict__ op, const double *__restrict__ dts,
-                                                const double *__restrict__ qts, const double *__restrict__ auxs,
-                                                double *__restrict__ Kws, double *__restrict__ kws, double *__restrict__ dxs,
-                                                double *__restrict__ wss, double *__restrict__ Kout, DevState *__restrict__ st,
-                                                int forward, int gmode, int iter) {
+// THE backward sweep: nodes t_hi - 1 ... t_lo of instance b, one wave.  The one-wave kernels below run it over [0, T) from the
+// terminal tile, the two-level kernels (agx_riccati_mx2.hpp) over one segment of the horizon.
+// vinit 0: V = 0 (element sweep of a segment), 1: V = terminal tile (+ regularisation), 2: V as given.
+// Vio: in (vinit 2) the value function of node t_hi, out the one of node t_lo.  bad: a pivot of the sweep was not positive.
+// CLOOP: the transition A / At (and, ELEM, the Gramian Cm) under the sweep's gains is accumulated; without it Am, At, Cm are
+// not touched.  s_dt: kMaxHorizon doubles of LDS owned by the caller (one array per kernel), filled here.
+template <int NV, bool GAINS, bool CLOOP, bool ELEM, class TLo>
+__device__ __forceinline__ void riccati_mx_seg(const int b, const DevOcp *__restrict__ op, const double *__restrict__ dts,
+                                               const double *__restrict__ qts, const double *__restrict__ auxs,
+                                               double *__restrict__ Kws, double *__restrict__ kws, double *__restrict__ Kout,
+                                               const double dreg, const TLo t_lo_, const int t_hi, const int vinit, mx4 &Vio, mx4 &Am,
+                                               mx4 &At, mx4 &Cm, bool &bad, lds_double *s_dt) {
   static_assert(NV <= 7, "16-column tiles: 7 joints + the gradient slot per half");
   typedef QT<NV> Q;
   typedef AUX<NV> A;
   constexpr int NX = 2 * NV, TS = Q::SIZE, LD = Q::LD;
   constexpr int Z = Q::cost + 1;  // zero of every tile: the cost line is 8 doubles, only [0] is ever written (buffers are cleared on allocation)
   const DevOcp &o = *op;
-  const int T = o.T, lane = threadIdx.x;
-  DevState &S = st[b];
-  // which instances sweep: as riccati_body
-  if (!GAINS && (S.done || S.admm_conv)) return;
-  if (GAINS && (gmode == 1 || gmode == 4) && S.done) return;  // gmode 4: see riccati_body
-  if (GAINS && gmode == 2 && S.gains_iter == S.dir_iter) return;
-  const double dreg = (GAINS && gmode != 1 && gmode != 4) ? (S.solved ? S.dreg : S.gains_dreg) : S.dreg;
-  if (GAINS && gmode != 0 && lane == 0) S.gains_iter = (gmode == 1) ? iter : S.dir_iter;
+  const int T = o.T, lane = threadIdx.x, t_lo = t_lo_;
   const double sig = GAINS ? kSigma : 0.0;
   const double *qb = qts + (long long)b * (T + 1) * TS;
   const double *ab = auxs + (long long)b * (T + 1) * A::SIZE;
@@ -165,8 +150,7 @@ __device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *__res
   }
 
   struct Tile { double hxx[4], hwx[2], hww[2], fb[4], tx[2], mt[2]; };
-  __shared__ double s_dt[kMaxHorizon];
-  stage_dts(s_dt, dts, T);
+  stage_dts((double *)s_dt, dts, T);
   auto load_tile = [&](Tile &z, int t) {
     const int sl = tile_slot(o, t);  // wave-uniform: scalar registers
     const double *tl = qb + (long long)sl * TS;
@@ -187,14 +171,23 @@ __device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *__res
     }
   };
 
-  // value function of node t+1: the terminal tile (+ regularisation)
+  // value function of node t_hi
   mx4 V;
-  {
+  if (vinit == 1) {
     const double *tt = qb + (long long)T * TS;
 #pragma unroll
     for (int r = 0; r < 4; ++r) V[r] = tt[oHxx[r]] + dg[r];
+  } else if (vinit == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) V[r] = 0.0;
+  } else {
+    V = Vio;
   }
   bool bad_pivot = false;
+  if constexpr (CLOOP) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { Am[r] = 2.0 * ih[r]; At[r] = 2.0 * ih[r]; Cm[r] = 0.0; }  // identity on the real indices
+  }
 
   auto step = [&](Tile &z, int t) {
     const double h = s_dt[t], h2 = h * h;
@@ -252,28 +245,28 @@ __device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *__res
       C[2] = ((Hxx[2] + dg[2]) + W1[2]) + h * W1[0];
       C[3] = ((Hxx[3] + dg[3]) + W1[3]) + h3 * W1[1];
     }
-    // ---- Gauss-Jordan over the acceleration rows [Mww | Mwx]
+    // ---- Gauss-Jordan over the acceleration rows [Mww | Mwx]  (CLOOP / ELEM: | G' A' as 16 more right-hand sides)
     double rpr[2] = {0.0, 0.0};
+    double GAt[2] = {0.0, 0.0}, Wz[2] = {0.0, 0.0};
+    if constexpr (CLOOP) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) { GAt[s] = h2 * At[s] + h * At[s + 2]; Wz[s] = GAt[s]; }
+    }
     auto pivot = [&](auto Kc) {
       constexpr int k = decltype(Kc)::value;
       if constexpr (k < NV) {
         constexpr int s = k >> 2, gk = k & 3;
         const double piv = readlane_f64(Ww[s], 16 * gk + k);
-#ifdef AGX_MX_OLD_CHAIN
-        const double rp = fast_rcp(piv);
-#else
         const double rp = chain_rcp(piv);
-#endif
-#ifdef AGX_MX_PERMLANE  // measured slower (round 3): direction sweep 0.209 -> 0.222 ms, batch-1 step 0.325 -> 0.358 ms
-        const double rW = bcast_group<gk>(Ww[s]), rX = bcast_group<gk>(Wx[s]);
-#else
         const double rW = __shfl(Ww[s], 16 * gk + j, 64), rX = __shfl(Wx[s], 16 * gk + j, 64);  // pivot row: lane (gk, j) to every group
-#endif
+        double rZ = 0.0;
+        if constexpr (ELEM) rZ = __shfl(Wz[s], 16 * gk + j, 64);  // the extra right-hand sides G' A' ride along
         // column k of my rows, with the pivot row's own entry zeroed (it is left untouched): off the reciprocal's chain
         const double c0 = row_bcast<k>(Ww[0]) * (s == 0 ? nz[gk] : 1.0), c1 = row_bcast<k>(Ww[1]) * (s == 1 ? nz[gk] : 1.0);
         const double f0 = c0 * rp, f1 = c1 * rp;
         Ww[0] -= f0 * rW; Wx[0] -= f0 * rX;
         Ww[1] -= f1 * rW; Wx[1] -= f1 * rX;
+        if constexpr (ELEM) { Wz[0] -= f0 * rZ; Wz[1] -= f1 * rZ; }
         rpr[s] += rp * ez[gk];
       }
     };
@@ -286,7 +279,35 @@ __device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *__res
     // V of node t = Mxx - Mwx' Kw
     V = __builtin_amdgcn_mfma_f64_16x16x4f64(Ax0, flip_sign(K0), C, 0, 0, 0);
     V = __builtin_amdgcn_mfma_f64_16x16x4f64(Ax1, flip_sign(K1), V, 0, 0, 0);
-    if (!GAINS) {
+    if constexpr (CLOOP) {
+      // transition of the segment under these gains, x_end = A x_t + beta (beta = column 7 of A), both as A (rows x_end,
+      // columns x_t) and as its transpose At (the products below need the summed index first):
+      //   A  <- A (Phi - G Kw) + (A f - A G kw) e7'  =  A Phi  +  At' F  -  (G'At)' Kw     (F: f in column 7)
+      //   At <- (Phi - G Kw)' At                      =  Phi' At  -  Kw' (G'At)
+      // and, ELEM, the Gramian  Cm <- Cm + (A G) Mww^-1 (A G)'  =  Cm + (G'At)' Z,  Z = Mww^-1 G'At out of the elimination.
+      const double nK0 = flip_sign(K0), nK1 = flip_sign(K1);
+      mx4 An;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) An[r] = Am[r] + hhi * row_ror8(Am[r]);
+      if (!GAINS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) An = __builtin_amdgcn_mfma_f64_16x16x4f64(At[r], z.fb[r], An, 0, 0, 0);
+      }
+      An = __builtin_amdgcn_mfma_f64_16x16x4f64(GAt[0], nK0, An, 0, 0, 0);
+      An = __builtin_amdgcn_mfma_f64_16x16x4f64(GAt[1], nK1, An, 0, 0, 0);
+      mx4 Atn = {At[0], At[1], At[2] + h * At[0], At[3] + h3 * At[1]};
+      Atn = __builtin_amdgcn_mfma_f64_16x16x4f64(K0, flip_sign(GAt[0]), Atn, 0, 0, 0);
+      Atn = __builtin_amdgcn_mfma_f64_16x16x4f64(K1, flip_sign(GAt[1]), Atn, 0, 0, 0);
+      if constexpr (ELEM) {
+        const double Z0 = Wz[0] * rpr[0], Z1 = Wz[1] * rpr[1];
+        Cm = __builtin_amdgcn_mfma_f64_16x16x4f64(GAt[0], Z0, Cm, 0, 0, 0);
+        Cm = __builtin_amdgcn_mfma_f64_16x16x4f64(GAt[1], Z1, Cm, 0, 0, 0);
+      }
+      Am = An; At = Atn;
+    }
+    if constexpr (ELEM) {
+      // gains of the zero-terminal problem: not the solver's, nothing is stored
+    } else if (!GAINS) {
       if (stV[0]) stP[0][(long long)t * stK[0]] = K0;
       if (stV[1]) stP[1][(long long)t * stK[1]] = K1;
     } else {
@@ -301,27 +322,53 @@ __device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *__res
     // the end).  Either a live old value or a branch makes the loaded values reach the next pass through register
     // copies at the loop latch, and the s_waitcnt vmcnt(0) in front of those copies drains the prefetch queue.
     prefetch_group_begin();
-    load_tile(z, t >= kMxDepth ? t - kMxDepth : 0);
+    load_tile(z, t - kMxDepth >= t_lo ? t - kMxDepth : t_lo);
     prefetch_group_end();
   };
 
-  int t = T - 1;
+  int t = t_hi - 1;
   // the nodes that do not fill a group of kMxDepth first, one at a time; the pipelined loop then runs whole groups
-  for (int r = T % kMxDepth; r > 0; --r, --t) {
+  for (int r = (t_hi - t_lo) % kMxDepth; r > 0; --r, --t) {
     Tile z;
     load_tile(z, t);
     step(z, t);
   }
-  if (t >= 0) {
+  if (t >= t_lo) {
     Tile tl[kMxDepth];
 #pragma unroll
     for (int i = 0; i < kMxDepth; ++i) load_tile(tl[i], t - i);
     prefetch_queue_settle(tl);
-    for (; t >= 0; t -= kMxDepth) {
+    for (; t >= t_lo; t -= kMxDepth) {
 #pragma unroll
       for (int i = 0; i < kMxDepth; ++i) step(tl[i], t - i);
     }
   }
+  Vio = V;
+  bad = bad_pivot;
+}
+
+// The one-wave sweep of an instance: which instances sweep and with which regularisation, the sweep over the whole horizon,
+// the breakdown flags, the forward pass.  __restrict__ sits on the pointers this function dereferences itself or hands to the
+// forward pass; the others are qualified where they are used, in riccati_mx_seg (qualified at both levels the compiler tracks
+// two nested sets of alias scopes, and the one-wave kernels come out differently scheduled for no gain).
+template <int NV, bool GAINS>
+__device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *op, const double *dts, const double *qts, const double *auxs,
+                                                double *Kws, double *kws, double *__restrict__ dxs, double *__restrict__ wss,
+                                                double *Kout, DevState *__restrict__ st, int forward, int gmode, int iter) {
+  constexpr int NX = 2 * NV, TS = QT<NV>::SIZE;
+  const DevOcp &o = *op;
+  const int T = o.T, lane = threadIdx.x;
+  DevState &S = st[b];
+  // which instances sweep: as riccati_body
+  if (!GAINS && (S.done || S.admm_conv)) return;
+  if (GAINS && (gmode == 1 || gmode == 4) && S.done) return;  // gmode 4: see riccati_body
+  if (GAINS && gmode == 2 && S.gains_iter == S.dir_iter) return;
+  const double dreg = (GAINS && gmode != 1 && gmode != 4) ? (S.solved ? S.dreg : S.gains_dreg) : S.dreg;
+  if (GAINS && gmode != 0 && lane == 0) S.gains_iter = (gmode == 1) ? iter : S.dir_iter;
+  __shared__ double s_dt[kMaxHorizon];
+  mx4 V, Am, At, Cm;  // Am, At, Cm: not touched without CLOOP
+  bool bad_pivot = false;
+  riccati_mx_seg<NV, GAINS, false, false>(b, op, dts, qts, auxs, Kws, kws, Kout, dreg, std::integral_constant<int, 0>(), T, /*vinit*/ 1, V, Am, At, Cm, bad_pivot, (lds_double *)s_dt);
   if (!GAINS) {
     // gmode 3: the LQR pass next to the ADMM factorisation of the same instance -- that sweep owns dir_fail (as it
     // does when it runs afterwards); the sticky "a direction was discarded" bit is raised by both
@@ -332,6 +379,7 @@ __device__ __forceinline__ void riccati_mx_body(const int b, const DevOcp *__res
     }
   }
   if (GAINS || !forward) return;
+  const double *qb = qts + (long long)b * (T + 1) * TS;
   riccati_forward<NV>(o, b, T, dts, qb, Kws + (long long)b * T * NV * NX, kws + (long long)b * T * NV, dxs, wss, s_dt);
 }
 
