@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "agx_traj_cartesian_sine_create", "agx_ocp_set_refs_async", "agx_ocp_refs_activate", "agx_ocp_refs_wait", "agx_host_alloc", "agx_host_free",
     "agx_ocp_download_async", "agx_ocp_download_wait",
     "agx_traj_generic_create_weighted", "agx_traj_cartesian_sine_wi_create", "agx_traj_get_tile",
+    "agx_ocp_set_plant_inertials", "agx_model_sensitivity",
 ]  # fmt: skip
 
 
@@ -499,3 +500,38 @@ class HipOcp:
         """u = us[0] + K[0] (x0 - x) on the model for n_substeps of dt_sub; the end state becomes x0."""
         d = None if disturbance is None else _f8(disturbance).reshape(self.B, self.nu)
         _chk(lib().agx_ocp_feedback_rollout(self._h, int(n_substeps), C.c_double(dt_sub), _p(d)))
+
+    # -- plant of the closed loop ---------------------------------------------
+    def _plant_arg(self, name, a, tail):
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        want = (self.B, self.nv) + tail
+        if tail == (9,) and a.shape == (self.B, self.nv, 3, 3):
+            a = a.reshape(want)
+        if a.shape != want:
+            raise ValueError(f"{name}: expected shape {want}, got {a.shape}")
+        return a
+
+    def set_plant_inertials(self, mass, com, inertia, armature=None):
+        """Per-instance link inertials of the robot feedback_rollout simulates (`workloads.stack_inertials` of B tables):
+        mass [B][nv], com [B][nv][3], inertia [B][nv][9] (or [B][nv][3][3]), armature [B][nv] (None: the model's).  The
+        controller keeps its own model."""
+        mass, com, inertia = self._plant_arg("mass", mass, ()), self._plant_arg("com", com, (3,)), self._plant_arg("inertia", inertia, (9,))
+        arm = None if armature is None else self._plant_arg("armature", armature, ())
+        _chk(lib().agx_ocp_set_plant_inertials(self._h, _p(mass), _p(com), _p(inertia), _p(arm)))
+
+    def clear_plant_inertials(self):
+        """feedback_rollout simulates the controller's own model again."""
+        _chk(lib().agx_ocp_set_plant_inertials(self._h, None, None, None, None))
+
+    def model_sensitivity(self, x, u, dt, delta_inertia=0.01, delta_com=0.01, delta_mass=0.01):
+        """[n][2 nv][10 nv] sensitivity of the Euler node's next state to the link inertials of the controller's model at the
+        samples x [n][nx], u [n][nu] (agx_model_sensitivity; `workloads.sensitivity_columns` labels the columns)."""
+        x, u = np.ascontiguousarray(np.asarray(x, dtype=np.float64)), np.ascontiguousarray(np.asarray(u, dtype=np.float64))
+        if x.ndim != 2 or x.shape[1] != self.nx or x.shape[0] < 1:
+            raise ValueError(f"x: expected shape (n, {self.nx}), got {x.shape}")
+        if u.shape != (x.shape[0], self.nu):
+            raise ValueError(f"u: expected shape ({x.shape[0]}, {self.nu}), got {u.shape}")
+        out = np.empty((x.shape[0], 2 * self.nv, 10 * self.nv))
+        _chk(lib().agx_model_sensitivity(self._h, int(x.shape[0]), C.c_double(dt), _p(x), _p(u), C.c_double(delta_inertia),
+                                         C.c_double(delta_com), C.c_double(delta_mass), _p(out)))
+        return out

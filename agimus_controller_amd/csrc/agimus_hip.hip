@@ -140,6 +140,10 @@ struct agx_ocp {
   int first_stride = 0;
   double *d_scratch = nullptr;
   size_t scratch_bytes = 0;
+  // plant of the closed loop (agx_ocp_set_plant_inertials): agx::PlantInertials<nv>[B], read by k_plant_rollout only
+  double *d_plant = nullptr;
+  bool plant_set = false;
+  std::vector<double> plant_stage;  // host image of d_plant (the upload reads it after the setter has returned the caller's arrays)
   RefView rv{};
   // resident trajectory
   double *d_traj = nullptr, *d_pts = nullptr;
@@ -665,6 +669,22 @@ int reset_state(agx_ocp *o) {
   hipLaunchKernelGGL(agx::k_reset_state, dim3((o->B + 255) / 256), dim3(256), 0, o->stream, o->d_state, o->B, o->d_ndone);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// the rollout the handle's plant asks for: k_feedback_rollout on the controller's own model, k_plant_rollout once a plant is set
+int launch_rollout(agx_ocp *o, int n_substeps, double dt_sub, const double *d_dist) {
+  return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
+    constexpr int NV = decltype(NVc)::value;
+    constexpr bool CH = decltype(CHc)::value;
+    if (o->plant_set)
+      hipLaunchKernelGGL((agx::k_plant_rollout<NV, CH>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model,
+                         (const agx::PlantInertials<NV> *)o->d_plant, o->d_us, o->d_Kout, o->d_x0, d_dist, o->B, o->T, n_substeps, dt_sub);
+    else
+      hipLaunchKernelGGL((agx::k_feedback_rollout<NV, CH>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model, o->d_us, o->d_Kout, o->d_x0,
+                         d_dist, o->B, o->T, n_substeps, dt_sub);
+    HIPCHK(hipGetLastError());
+    return 0;
+  });
 }
 
 int prof_mark(agx_ocp *o, int kind, bool start) {
@@ -1499,7 +1519,7 @@ void agx_ocp_destroy(agx_ocp *o) {
   if (o->copy_stream) (void)hipStreamSynchronize(o->copy_stream);
   void *ptrs[] = {o->d_mx2_elem, o->d_mx2_bnd, o->d_mx2_cl, o->d_ref_back, o->d_frames_back, o->d_snap, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us, o->d_x0, o->d_tiles, o->d_Kws, o->d_kws, o->d_Kout, o->d_dx,
                   o->d_du, o->d_ref, o->d_frames, o->d_state, o->d_ndone, o->d_scratch, o->d_traj, o->d_pts, o->d_sine, o->d_qt, o->d_aux, o->d_w, o->d_nodestat,
-                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr};
+                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr, o->d_plant};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (o->h_ndone) (void)hipHostFree(o->h_ndone);
@@ -2077,6 +2097,12 @@ int agx_ocp_time_kernel(agx_ocp *o, int which, int reps, double *avg_ms) {
   if (reset_state(o)) return -1;
   if (which == 1 || which == 2 || which == 5 || which == 6 || which == 7) { if (launch_calc_qp(o)) return -1; }
   if (which == 2) { if (launch_riccati(o, 1, 0)) return -1; }
+  double *d_x0_keep = nullptr;
+  if (which == 8) {  // every rollout moves x0: the timed ones start from where the last one ended, the caller's x0 comes back afterwards
+    if (ensure_scratch(o, sizeof(double) * o->B * o->nx)) return -1;
+    d_x0_keep = o->d_scratch;
+    HIPCHK(hipMemcpyAsync(d_x0_keep, o->d_x0, sizeof(double) * o->B * o->nx, hipMemcpyDeviceToDevice, o->stream));
+  }
   // warm-up launch, then `reps` timed launches bracketed by events on the problem's stream
   for (int pass = 0; pass < 2; ++pass) {
     const int n = pass == 0 ? 1 : reps;
@@ -2091,10 +2117,15 @@ int agx_ocp_time_kernel(agx_ocp *o, int which, int reps, double *avg_ms) {
       else if (which == 5) rc = launch_riccati(o, 0, 0);
       else if (which == 6) rc = launch_gains(o);
       else if (which == 7) rc = launch_riccati(o, 1, true, 1);
+      else if (which == 8) rc = launch_rollout(o, 10, 1e-3, nullptr);
       else return fail("agx_ocp_time_kernel: unknown kernel");
       if (rc) return rc;
     }
     if (pass == 1) HIPCHK(hipEventRecord(o->ev1, o->stream));
+    HIPCHK(hipStreamSynchronize(o->stream));
+  }
+  if (d_x0_keep) {
+    HIPCHK(hipMemcpyAsync(o->d_x0, d_x0_keep, sizeof(double) * o->B * o->nx, hipMemcpyDeviceToDevice, o->stream));
     HIPCHK(hipStreamSynchronize(o->stream));
   }
   float ms = 0.f;
@@ -2476,15 +2507,76 @@ int agx_ocp_feedback_rollout(agx_ocp *o, int n_substeps, double dt_sub, const do
     d_dist = o->d_scratch;
     if (up(o, d_dist, disturbance, o->B, 1)) return -1;
   }
-  return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
+  if (launch_rollout(o, n_substeps, dt_sub, d_dist)) return -1;
+  if (disturbance) HIPCHK(hipStreamSynchronize(o->stream));  // the caller may reuse its buffer
+  return 0;
+}
+
+int agx_ocp_set_plant_inertials(agx_ocp *o, const double *mass, const double *com, const double *inertia, const double *armature) {
+  if (!o) return fail("null handle");
+  if (!mass && !com && !inertia && !armature) {  // back to the controller's own model; d_plant stays allocated for the next plant
+    o->plant_set = false;
+    return 0;
+  }
+  if (!mass || !com || !inertia) return fail("agx_ocp_set_plant_inertials: mass, com and inertia go together (all NULL clears the plant)");
+  const size_t B = o->B, nv = o->nv, nvu = o->nvu, w = 14 * nv;  // agx::PlantInertials<nv>: mass nv | com 3 nv | inertia 9 nv | armature nv
+  for (size_t k = 0; k < B * nvu; ++k) {
+    if (!std::isfinite(mass[k]) || (armature && !std::isfinite(armature[k])))
+      return fail("agx_ocp_set_plant_inertials: non-finite mass or armature (instance " + std::to_string(k / nvu) + ", joint " + std::to_string(k % nvu) + ")");
+    if (mass[k] < 0.0) return fail("agx_ocp_set_plant_inertials: negative mass (instance " + std::to_string(k / nvu) + ", joint " + std::to_string(k % nvu) + ")");
+    if (armature && armature[k] < 0.0)
+      return fail("agx_ocp_set_plant_inertials: negative armature (instance " + std::to_string(k / nvu) + ", joint " + std::to_string(k % nvu) + ")");
+  }
+  for (size_t k = 0; k < B * nvu * 3; ++k)
+    if (!std::isfinite(com[k])) return fail("agx_ocp_set_plant_inertials: non-finite com (instance " + std::to_string(k / (3 * nvu)) + ")");
+  for (size_t k = 0; k < B * nvu * 9; ++k)
+    if (!std::isfinite(inertia[k])) return fail("agx_ocp_set_plant_inertials: non-finite inertia (instance " + std::to_string(k / (9 * nvu)) + ")");
+  if (set_device(o)) return -1;
+  if (!o->d_plant) HIPCHK(hipMalloc((void **)&o->d_plant, sizeof(double) * B * w));
+  // a rollout queued earlier may still read d_plant, and the copy below reads plant_stage: both are the handle's own, so the
+  // host waits for the stream before it rewrites the image, then uploads IN the solver's stream, behind everything queued
+  HIPCHK(hipStreamSynchronize(o->stream));
+  o->plant_stage.assign(B * w, 0.0);
+  for (size_t b = 0; b < B; ++b) {
+    double *p = o->plant_stage.data() + b * w, *pc = p + nv, *pi = pc + 3 * nv, *pa = pi + 9 * nv;
+    for (size_t i = 0; i < nvu; ++i) {
+      p[i] = mass[b * nvu + i];
+      std::memcpy(pc + 3 * i, com + (b * nvu + i) * 3, sizeof(double) * 3);
+      std::memcpy(pi + 9 * i, inertia + (b * nvu + i) * 9, sizeof(double) * 9);
+      pa[i] = armature ? armature[b * nvu + i] : o->hm.armature[i];
+    }
+    for (size_t i = nvu; i < nv; ++i) pa[i] = o->hm.armature[i];  // pad joints: massless, the armature of the padding
+  }
+  HIPCHK(hipMemcpyAsync(o->d_plant, o->plant_stage.data(), sizeof(double) * B * w, hipMemcpyHostToDevice, o->stream));
+  HIPCHK(hipStreamSynchronize(o->stream));
+  o->plant_set = true;
+  return 0;
+}
+
+int agx_model_sensitivity(agx_ocp *o, int n, double dt, const double *x, const double *u, double delta_inertia, double delta_com,
+                          double delta_mass, double *out) {
+  if (!o || !x || !u || !out) return fail("agx_model_sensitivity: null argument");
+  if (n < 1) return fail("agx_model_sensitivity: n must be positive");
+  if (!(dt > 0.0) || !std::isfinite(dt)) return fail("agx_model_sensitivity: dt must be positive");
+  for (double d : {delta_inertia, delta_com, delta_mass})
+    if (d == 0.0 || !std::isfinite(d)) return fail("agx_model_sensitivity: the deltas must be finite and not zero");
+  if (set_device(o)) return -1;
+  const size_t n_out = (size_t)n * 2 * o->nvu * 10 * o->nvu;
+  if (ensure_scratch(o, sizeof(double) * ((size_t)n * (o->nx + o->nu) + n_out))) return -1;
+  double *dx = o->d_scratch, *du = dx + (size_t)n * o->nx, *dout = du + (size_t)n * o->nu;
+  if (up(o, dx, x, n, 2) || up(o, du, u, n, 1)) return -1;
+  int rc = dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
-    hipLaunchKernelGGL((agx::k_feedback_rollout<NV, CH>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model, o->d_us, o->d_Kout, o->d_x0,
-                       d_dist, o->B, o->T, n_substeps, dt_sub);
+    hipLaunchKernelGGL((agx::k_model_sensitivity<NV, CH>), dim3(n), dim3(agx::kSensitivityLanes<NV>), 0, o->stream, o->d_model, o->nvu, dt, dx, du,
+                       delta_inertia, delta_com, delta_mass, dout);
     HIPCHK(hipGetLastError());
-    if (disturbance) HIPCHK(hipStreamSynchronize(o->stream));  // the caller may reuse its buffer
     return 0;
   });
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * n_out, hipMemcpyDeviceToHost, o->stream));
+  HIPCHK(hipStreamSynchronize(o->stream));
+  return 0;
 }
 
 int agx_ocp_mpc_step(agx_ocp *o, int k0, int max_iter, int first) {

@@ -367,6 +367,105 @@ AGX_UNROLL_NV
   }
 }
 
+// ------------------------------------------------------------------ other inertial sources
+// body_inertia / bias_and_inertia above read a link's inertials from the model's own table, and every kernel of the solver
+// calls those.  The overloads below take them from a source instead: the plant of the closed loop from PlantInertials[b] of
+// its instance, the sensitivity sweep from the model with one entry moved (PerturbedInertials, agx_kernels.hpp).  A source
+// gives mass_of(i), com_of(i, e), inertia_of(i, e) (row major, about the com, joint frame) and armature_of(i); the kinematic
+// tree, the axes and gravity are always the model's.  The arithmetic is that of the routines above, operation for operation.
+
+// Inertials of ONE plant instance at the compiled capacity NV, laid out as the model's table (RobotTable / DevModel): the pad
+// joints of a model below the capacity are massless and carry the armature the padding gives them.
+template <int NV>
+struct PlantInertials {
+  double mass[NV];
+  double com[NV][3];
+  double inertia[NV][9];
+  double armature[NV];
+  AGX_DEV double mass_of(int i) const { return mass[i]; }
+  AGX_DEV double com_of(int i, int e) const { return com[i][e]; }
+  AGX_DEV double inertia_of(int i, int e) const { return inertia[i][e]; }
+  AGX_DEV double armature_of(int i) const { return armature[i]; }
+};
+
+template <int NV, class INERTIALS>
+AGX_DEV void body_inertia(const INERTIALS &in, const Kin<NV> &k, int i, double *I) {
+  const double cl[3] = {in.com_of(i, 0), in.com_of(i, 1), in.com_of(i, 2)};
+  double Il[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) Il[e] = in.inertia_of(i, e);
+  double c[3];
+  mv3(k.R[i], cl, c);
+  c[0] += k.p[i][0]; c[1] += k.p[i][1]; c[2] += k.p[i][2];
+  const double ms = in.mass_of(i);
+  double T[9], Iw[9];
+  mm3(k.R[i], Il, T);
+  // Iw = T R^T
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) Iw[3 * a + b] = T[3 * a] * k.R[i][3 * b] + T[3 * a + 1] * k.R[i][3 * b + 1] + T[3 * a + 2] * k.R[i][3 * b + 2];
+  const double cc = dot3(c, c);
+  I[0] = ms;
+  I[1] = ms * c[0]; I[2] = ms * c[1]; I[3] = ms * c[2];
+  I[4] = Iw[0] + ms * (cc - c[0] * c[0]);
+  I[5] = 0.5 * (Iw[1] + Iw[3]) - ms * c[0] * c[1];
+  I[6] = 0.5 * (Iw[2] + Iw[6]) - ms * c[0] * c[2];
+  I[7] = Iw[4] + ms * (cc - c[1] * c[1]);
+  I[8] = 0.5 * (Iw[5] + Iw[7]) - ms * c[1] * c[2];
+  I[9] = Iw[8] + ms * (cc - c[2] * c[2]);
+}
+template <int NV, bool CHAIN, class INERTIALS>
+AGX_DEV void bias_and_inertia(const DevModel &m, const INERTIALS &in, const Kin<NV> &k, const double *qd, Dyn<NV> &d, double *nle,
+                              double (*M)[NV]) {
+  double f[NV][6];
+AGX_UNROLL_NV
+  for (int i = 0; i < NV; ++i) {
+    const int par = parent_of<NV, CHAIN>(m, i);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) d.v[i][e] = (par >= 0 ? d.v[par][e] : 0.0) + k.S[i][e] * qd[i];
+    mcross(d.v[i], k.S[i], d.Sd[i]);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) d.a0[i][e] = (par >= 0 ? d.a0[par][e] : (e < 3 ? -m.gravity[e] : 0.0)) + d.Sd[i][e] * qd[i];
+    body_inertia<NV>(in, k, i, d.Ib[i]);
+#pragma unroll
+    for (int e = 0; e < 10; ++e) d.Ic[i][e] = d.Ib[i][e];
+    double h[6], g[6], x[6];
+    iapply(d.Ib[i], d.v[i], h);
+    iapply(d.Ib[i], d.a0[i], g);
+    fcross(d.v[i], h, x);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) f[i][e] = g[e] + x[e];
+  }
+#pragma unroll
+  for (int i = NV - 1; i >= 0; --i) {
+    nle[i] = dot6(k.S[i], f[i]);
+    double m6[6];
+    iapply(d.Ic[i], k.S[i], m6);
+AGX_UNROLL_NV
+    for (int j = 0; j < NV; ++j) {
+      if (j <= i || !CHAIN) {
+        if (j == i) {
+          M[i][i] = dot6(k.S[i], m6) + in.armature_of(i);
+        } else if (is_anc<NV, CHAIN>(m, i, j)) {
+          const double val = dot6(k.S[j], m6);
+          M[i][j] = val;
+          M[j][i] = val;
+        } else if (!CHAIN && !is_anc<NV, CHAIN>(m, j, i)) {
+          M[i][j] = 0.0;  // different branches
+        }
+      }
+    }
+    const int par = parent_of<NV, CHAIN>(m, i);
+    if (par >= 0) {
+#pragma unroll
+      for (int e = 0; e < 6; ++e) f[par][e] += f[i][e];
+#pragma unroll
+      for (int e = 0; e < 10; ++e) d.Ic[par][e] += d.Ic[i][e];
+    }
+  }
+}
+
 // In-place lower Cholesky of a dense NV x NV SPD matrix (registers), then
 // explicit inverse Minv = L^-T L^-1.
 // x = A^-1 b for a symmetric positive definite A (destroyed): Cholesky + two triangular solves.

@@ -1482,6 +1482,140 @@ AGX_UNROLL_NV
   for (int e = 0; e < NX; ++e) x0[(long long)b * NX + e] = x[e];
 }
 
+// Joint accelerations of the model's kinematic tree carrying the inertials of `in`: the forward dynamics of
+// node_calc_running (world-frame bias torques and joint-space inertia, explicit inverse) with another inertial source.
+template <int NV, bool CHAIN, class INERTIALS>
+AGX_DEV void forward_dynamics_with(const DevModel &m, const INERTIALS &in, const double *x, const double *u, double *a) {
+  Kin<NV> k;
+  kinematics<NV, CHAIN>(m, x, k);
+  Dyn<NV> d;
+  double nle[NV], M[NV][NV], Minv[NV][NV];
+  bias_and_inertia<NV, CHAIN>(m, in, k, x + NV, d, nle, M);
+  spd_inverse<NV>(M, Minv);
+AGX_UNROLL_NV
+  for (int i = 0; i < NV; ++i) {
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc += Minv[i][j] * (u[j] - nle[j]);
+    a[i] = acc;
+  }
+}
+
+// k_feedback_rollout against a plant that is not the controller's model: instance b integrates the forward dynamics of
+// plant[b] (mass, centre of mass, inertia and armature of every link; placements, axes, parents and gravity stay the
+// model's) under the same law, u = us[0] + tau_d + K[0] (x0 - x), with the same semi-implicit Euler sub-steps; the end state
+// becomes x0.  One instance per lane, as there; a lane reads its own 14 NV doubles from HBM in every sub-step.
+template <int NV, bool CHAIN>
+__global__ void __launch_bounds__(64) k_plant_rollout(const DevModel *__restrict__ mp, const PlantInertials<NV> *__restrict__ plant,
+                                                      const double *__restrict__ us, const double *__restrict__ Kout,
+                                                      double *__restrict__ x0, const double *__restrict__ disturbance, int B, int T,
+                                                      int n_sub, double dt_sub) {
+  constexpr int NX = 2 * NV, NU = NV;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const PlantInertials<NV> &in = plant[b];
+  double xr[NX], x[NX], u0[NU], K[NU][NX], tau_d[NU];
+#pragma unroll
+  for (int e = 0; e < NX; ++e) { xr[e] = x0[(long long)b * NX + e]; x[e] = xr[e]; }
+AGX_UNROLL_NV
+  for (int i = 0; i < NU; ++i) {
+    u0[i] = us[(long long)b * T * NU + i];
+    tau_d[i] = disturbance ? disturbance[(long long)b * NU + i] : 0.0;
+AGX_UNROLL_NV
+    for (int e = 0; e < NX; ++e) K[i][e] = Kout[(long long)b * T * NU * NX + i * NX + e];
+  }
+  for (int s = 0; s < n_sub; ++s) {
+    double u[NU], a[NV];
+AGX_UNROLL_NV
+    for (int i = 0; i < NU; ++i) {
+      double acc = u0[i] + tau_d[i];
+#pragma unroll
+      for (int e = 0; e < NX; ++e) acc += K[i][e] * (xr[e] - x[e]);
+      u[i] = acc;
+    }
+    forward_dynamics_with<NV, CHAIN>(*mp, in, x, u, a);
+AGX_UNROLL_NV
+    for (int i = 0; i < NV; ++i) {  // the update of node_calc_running, operation for operation
+      const double v = x[NV + i];
+      x[NV + i] = v + dt_sub * a[i];
+      x[i] = x[i] + dt_sub * v + dt_sub * dt_sub * a[i];
+    }
+  }
+AGX_UNROLL_NV
+  for (int e = 0; e < NX; ++e) x0[(long long)b * NX + e] = x[e];
+}
+
+// The model with ONE inertial entry of ONE link moved, as evaluate_model_sensibility.py:9-49 upstream perturbs it.
+// slot 0..5: inertia entry (row, col) = (0,0) (1,0) (1,1) (2,0) (2,1) (2,2), added at [row][col] AND at [col][row] as the script
+// does (a diagonal entry therefore moves by twice delta); 6..8: centre of mass x, y, z; 9: mass.  link < 0: the model as it is.
+struct PerturbedInertials {
+  const DevModel &m;
+  int link, slot;
+  double delta;
+  AGX_DEV double mass_of(int i) const { return (i == link && slot == 9) ? m.mass[i] + delta : m.mass[i]; }
+  AGX_DEV double com_of(int i, int e) const { return (i == link && slot == 6 + e) ? m.com[i][e] + delta : m.com[i][e]; }
+  AGX_DEV double inertia_of(int i, int e) const {
+    double v = m.inertia[i][e];
+    if (i == link && slot < 6) {
+      const int row = slot >= 3 ? 2 : (slot >= 1 ? 1 : 0), col = slot - row * (row + 1) / 2;
+      if (e == 3 * row + col) v += delta;
+      if (e == 3 * col + row) v += delta;
+    }
+    return v;
+  }
+  AGX_DEV double armature_of(int i) const { return m.armature[i]; }
+};
+
+// Sensitivity of the Euler node's next state to the inertials (evaluate_model_sensibility.py:97-119 upstream): for sample s
+//   out[s][r][10 l + k] = | xnext_r(model with entry k of link l moved by delta_k) - xnext_r(model) | / delta_k ,
+// xnext = [q + v+ dt ; v+], v+ = v + a dt, rows r and links l over the caller's nvu joints.  One workgroup per sample, one
+// lane per forward-dynamics evaluation: lanes 0 .. 10 nvu - 1 the columns, lane 10 nvu the unperturbed base, handed to the
+// others through LDS.  x [n][2 NV], u [n][NV] at the capacity, out [n][2 nvu][10 nvu].
+template <int NV>
+constexpr int kSensitivityLanes = NV <= 8 ? 128 : 384;  // >= 10 NV + 1
+template <int NV, bool CHAIN>
+__global__ void __launch_bounds__(kSensitivityLanes<NV>) k_model_sensitivity(const DevModel *__restrict__ mp, int nvu, double dt,
+                                                                             const double *__restrict__ x, const double *__restrict__ u,
+                                                                             double delta_inertia, double delta_com, double delta_mass,
+                                                                             double *__restrict__ out) {
+  static_assert(10 * NV + 1 <= kSensitivityLanes<NV>, "one lane per column and one for the base");
+  constexpr int NX = 2 * NV;
+  __shared__ double base[NX];
+  const long long s = blockIdx.x;
+  const int c = threadIdx.x, ncol = 10 * nvu;
+  const int slot = c % 10;
+  const double delta = slot < 6 ? delta_inertia : (slot < 9 ? delta_com : delta_mass);
+  double xn[NX];
+  if (c <= ncol) {
+    double xl[NX], ul[NV], a[NV];
+AGX_UNROLL_NV
+    for (int e = 0; e < NX; ++e) xl[e] = x[s * NX + e];
+AGX_UNROLL_NV
+    for (int e = 0; e < NV; ++e) ul[e] = u[s * NV + e];
+    const PerturbedInertials in{*mp, c < ncol ? c / 10 : -1, slot, delta};
+    forward_dynamics_with<NV, CHAIN>(*mp, in, xl, ul, a);
+AGX_UNROLL_NV
+    for (int i = 0; i < NV; ++i) {
+      xn[NV + i] = xl[NV + i] + a[i] * dt;
+      xn[i] = xl[i] + xn[NV + i] * dt;
+    }
+    if (c == ncol) {
+AGX_UNROLL_NV
+      for (int e = 0; e < NX; ++e) base[e] = xn[e];
+    }
+  }
+  __syncthreads();
+  if (c < ncol) {
+    double *o = out + s * 2 * nvu * ncol + c;
+AGX_UNROLL_NV
+    for (int i = 0; i < NV; ++i)
+      if (i < nvu) {
+        o[(long long)i * ncol] = fabs(xn[i] - base[i]) / delta;
+        o[(long long)(nvu + i) * ncol] = fabs(xn[NV + i] - base[NV + i]) / delta;
+      }
+  }
+}
+
 template <int NV, bool CHAIN>
 __global__ void k_rnea(const DevModel *__restrict__ mp, int n, const double *__restrict__ q, const double *__restrict__ v,
                        const double *__restrict__ a, double *__restrict__ tau) {

@@ -334,3 +334,85 @@ def weight_increasing_schedule(n_points: int, dt: float, p0, amp_xyz, period, ma
 
 # Weights of the reference's sine-wave test (tests/test_sin_wave_configuration_space.py:138-144).
 SINE_WEIGHTS = dict(w_q=1.0, w_qdot=0.1, w_effort=3e-4, w_pose=0.1)
+
+
+def plant_tables(table, B: int, seed: int, rel: float = 0.1, payload=None):
+    """B robot tables for the plants of a batch (`HipOcp.set_plant_inertials`): same kinematics, other inertials.  Entry 0
+    is `table` itself; with payload = (mass, com in the last link's joint frame) entry 1 carries that point mass lumped
+    into its last link; every other entry has the mass, centre of mass and inertia of every link moved by seeded relative
+    perturbations within +-rel (com relative to the largest com offset of the link; the inertia by a symmetric matrix
+    relative to its largest entry, so it stays symmetric)."""
+    import dataclasses
+
+    nv = table.nv
+    out = [table]
+    for b in range(1, B):
+        if b == 1 and payload is not None:
+            m2, c2 = float(payload[0]), np.asarray(payload[1], dtype=float)
+            mass, com, inertia = table.mass.copy(), table.com.copy(), table.inertia.reshape(nv, 9).copy()
+            m, c, I = rt.lump_inertia(mass[-1], com[-1], inertia[-1].reshape(3, 3), m2, c2, np.zeros((3, 3)))
+            mass[-1], com[-1], inertia[-1] = m, c, I.reshape(9)
+            out.append(dataclasses.replace(table, name=f"{table.name}_payload", mass=mass, com=com, inertia=inertia))
+            continue
+        rng = np.random.default_rng([seed, b])
+        mass = table.mass * (1.0 + rng.uniform(-rel, rel, nv))
+        com = table.com + np.abs(table.com).max(axis=1, keepdims=True) * rng.uniform(-rel, rel, (nv, 3))
+        inertia = table.inertia.reshape(nv, 3, 3).copy()
+        e = rng.uniform(-rel, rel, (nv, 3, 3))
+        inertia += np.abs(inertia).max(axis=(1, 2), keepdims=True) * 0.5 * (e + e.transpose(0, 2, 1))
+        inertia = 0.5 * (inertia + inertia.transpose(0, 2, 1))  # exactly symmetric, whatever rounding the input carries
+        out.append(dataclasses.replace(table, name=f"{table.name}_plant{b}", mass=mass, com=com, inertia=inertia.reshape(nv, 9)))
+    return out
+
+
+def stack_inertials(tables):
+    """mass [B][nv], com [B][nv][3], inertia [B][nv][9], armature [B][nv] of B tables: the arguments of
+    `HipOcp.set_plant_inertials`."""
+    nv = tables[0].nv
+    return (np.stack([np.asarray(t.mass, dtype=float).reshape(nv) for t in tables]),
+            np.stack([np.asarray(t.com, dtype=float).reshape(nv, 3) for t in tables]),
+            np.stack([np.asarray(t.inertia, dtype=float).reshape(nv, 9) for t in tables]),
+            np.stack([np.asarray(t.armature, dtype=float).reshape(nv) for t in tables]))
+
+
+SENSITIVITY_INERTIA_ENTRIES = ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2))
+
+
+def sensitivity_columns(nv: int):
+    """Labels of the 10 nv columns of `HipOcp.model_sensitivity`, in the order of the reference's
+    evaluate_model_sensibility.py: per link l six ("inertia", l, row, col), three ("com", l, i), one ("mass", l)."""
+    cols = []
+    for l in range(nv):
+        cols += [("inertia", l, r, c) for r, c in SENSITIVITY_INERTIA_ENTRIES]
+        cols += [("com", l, i) for i in range(3)]
+        cols.append(("mass", l))
+    return cols
+
+
+def perturb_inertial(table, label, delta: float):
+    """`table` with the entry a `sensitivity_columns` label names moved as evaluate_model_sensibility.py:9-49 moves it: an
+    inertia entry at [row][col] and at [col][row] (a diagonal entry therefore by 2 delta), a com coordinate, or the mass."""
+    import dataclasses
+
+    nv = table.nv
+    mass, com, inertia = table.mass.copy(), table.com.copy(), table.inertia.reshape(nv, 3, 3).copy()
+    if label[0] == "inertia":
+        _, l, row, col = label
+        inertia[l, row, col] += delta
+        inertia[l, col, row] += delta
+    elif label[0] == "com":
+        com[label[1], label[2]] += delta
+    else:
+        mass[label[1]] += delta
+    return dataclasses.replace(table, mass=mass, com=com, inertia=inertia.reshape(nv, 9))
+
+
+def load_state_control_points(path):
+    """x0 [n][nx], u0 [n][nu] of a file in the layout of the reference's state_and_control_expe_data.yaml
+    (point_1 .. point_n, each with the lists x0 and u0)."""
+    import yaml
+
+    with open(path) as f:
+        data = yaml.safe_load(f)
+    points = [data[f"point_{k}"] for k in range(1, len(data) + 1)]
+    return np.array([p["x0"] for p in points], dtype=float), np.array([p["u0"] for p in points], dtype=float)

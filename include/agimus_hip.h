@@ -279,6 +279,18 @@ int agx_model_frame_placement(agx_ocp *ocp, int n, int frame, const double *q, d
  * 1 LOCAL (the inverse kinematics of trajectories/sine_wave_cartesian_space.py:62-111 uses both). */
 int agx_model_frame_jacobian(agx_ocp *ocp, int n, int frame, int local, const double *q, double *J);
 
+/* Sensitivity of the Euler node to the link inertials of the controller's model, the study of
+ * agimus_controller_examples/main/model_sensibility/evaluate_model_sensibility.py:97-119, for n samples (host buffers
+ * x [n][nx], u [n][nu]): out [n][2 nv][10 nv],
+ *   out[s][r][10 l + k] = | xnext_r(model with entry k of link l moved) - xnext_r(model) | / delta ,
+ * xnext = [q + v+ dt; v+], v+ = v + a dt.  Entries of a link as the script orders and perturbs them (:9-49):
+ * k = 0..5 inertia (row, col) = (0,0) (1,0) (1,1) (2,0) (2,1) (2,2), delta_inertia added at [row][col] and at
+ * [col][row] -- a diagonal entry moves by 2 delta_inertia and is still divided by delta_inertia; k = 6..8 centre of
+ * mass x, y, z by delta_com; k = 9 mass by delta_mass.  A plant set on the handle plays no part.  Refuses n < 1,
+ * dt <= 0 and a zero delta.                                                                       */
+int agx_model_sensitivity(agx_ocp *ocp, int n, double dt, const double *x, const double *u,
+                          double delta_inertia, double delta_com, double delta_mass, double *out);
+
 /* Replaces the per-node residual copies of OCPCrocoGeneric.fill_debug_data
  * (ocp_croco_generic.py:840-853): residual of running row `row` at the resident
  * solution, out [B][T][nr].                                                    */
@@ -303,7 +315,9 @@ int agx_ocp_qp_tiles(agx_ocp *ocp, double *qt, double *aux, int *qt_size, int *a
  * which: 0 = derivative pass (running + terminal launches), 1 = Riccati backward + forward,
  * 2 = step kernel (du, KKT, line search; nothing committed), 3 = derivative pass over the running
  * nodes only (one launch), 4 = canonical-tile derivative pass (running nodes), 5 = Riccati backward
- * only, 6 = exit (gains) sweep alone, 7 = direction + speculative gains sweep in one launch.        */
+ * only, 6 = exit (gains) sweep alone, 7 = direction + speculative gains sweep in one launch,
+ * 8 = the closed-loop rollout of agx_ocp_feedback_rollout as the handle would launch it (10 sub-steps of
+ * 1 ms, no disturbance; with or without a plant), x0 restored afterwards.                          */
 int agx_ocp_time_kernel(agx_ocp *ocp, int which, int reps, double *avg_ms);
 
 /* In-situ kernel timing: while enabled, every solve brackets the launches of its SQP loop with
@@ -392,10 +406,23 @@ int agx_ocp_mpc_step(agx_ocp *ocp, int k0, int max_iter, int first);
 /* What consumes an MPC step: the linear feedback controller fed by
  * AgimusController.send_control_msg (agimus_controller_ros/agimus_controller.py:418-426) applies
  *   u = us[0] + K[0] (x0 - x_measured)
- * at the control rate.  Here the plant is the model: n_substeps semi-implicit Euler steps of dt_sub
+ * at the control rate.  Here the plant is the model (or the model with the inertials of
+ * agx_ocp_set_plant_inertials): n_substeps semi-implicit Euler steps of dt_sub
  * from the resident x0 under that law (+ an optional constant torque disturbance [B][nu], host);
  * the end state replaces x0, ready for agx_ocp_mpc_step(..., first = 2).           */
 int agx_ocp_feedback_rollout(agx_ocp *ocp, int n_substeps, double dt_sub, const double *disturbance);
+/* The plant of that closed loop, per instance: link inertials that differ from the controller's model (unknown payload,
+ * identified against nominal parameters, Monte-Carlo runs over parameter uncertainty).  Host arrays at the CALLER's nv:
+ * mass [B][nv], com [B][nv][3] (joint frame), inertia [B][nv][9] (about the com, joint frame, row major), armature [B][nv]
+ * (NULL: the model's).  Placements, axes, parents and gravity stay the model's, and so does everything the solver does:
+ * only agx_ocp_feedback_rollout reads the plant.  All four NULL: back to the controller's own model, exactly the rollout
+ * of a handle that never had a plant.  Non-finite values, a negative mass and a negative armature are refused (the handle
+ * keeps what it had); the inertia is NOT tested for positive definiteness.
+ * Ordering: the upload runs on the handle's solver stream (agx_ocp_set_stream), after the host has waited for the work
+ * queued there; the call returns once the copy is complete, so the arrays may be reused at once and every rollout queued
+ * before the call has used the old plant, every later one the new.                                                    */
+int agx_ocp_set_plant_inertials(agx_ocp *ocp, const double *mass, const double *com, const double *inertia,
+                                const double *armature);
 /* The resident initial state x0 [B][nx] (measured state of the next step).          */
 int agx_ocp_download_x0(agx_ocp *ocp, double *x0);
 
