@@ -13,6 +13,7 @@ import typing as T
 import numpy as np
 
 AGX_MAX_ROWS = 8
+AGX_MAX_COST_PAIRS = 64
 AGX_MAX_NV = 32
 
 # agx_residual_kind
@@ -217,6 +218,27 @@ class ConstraintSpec:
     name: str = ""
 
 
+def check_cost_rows(rows: T.Sequence[RowSpec], what: str = "node type", wide: bool = False) -> None:
+    """The rule of agx_ocp_create for one table of cost rows: up to AGX_MAX_ROWS rows of any kind, or -- a wide cost set -- up to
+    AGX_MAX_ROWS rows that are not collision rows in front of up to AGX_MAX_COST_PAIRS trailing collision rows.  ValueError otherwise.
+    wide: the other node type has more than AGX_MAX_ROWS rows; the set is then wide as a whole and this table follows the wide
+    rule whatever its length."""
+    if len(rows) <= AGX_MAX_ROWS and not wide:
+        return
+    coll = [r.kind == RES_COLLISION for r in rows]
+    if len(rows) - sum(coll) > AGX_MAX_ROWS:
+        raise ValueError(f"{what}: at most {AGX_MAX_ROWS} cost items that are not collision pairs are supported (AGX_MAX_ROWS)")
+    if sum(coll) > AGX_MAX_COST_PAIRS:
+        raise ValueError(f"{what}: at most {AGX_MAX_COST_PAIRS} collision-pair cost items are supported (AGX_MAX_COST_PAIRS)")
+    seen = None
+    for i, (r, c) in enumerate(zip(rows, coll)):
+        if c and seen is None:
+            seen = i
+        elif not c and seen is not None:
+            raise ValueError(f"{what}: with more than {AGX_MAX_ROWS} cost items in a node type the collision pairs must come last: "
+                             f"item {seen} ('{rows[seen].name}') has '{r.name}' (item {i}) behind it")
+
+
 def row_offsets(rows: T.Sequence[RowSpec], nv: int) -> list[int]:
     offs, off = [], 0
     for r in rows:
@@ -301,7 +323,9 @@ class PackedOcp:
         running_constraints: T.Sequence[ConstraintSpec] = (),
         terminal_constraints: T.Sequence[ConstraintSpec] = (),
     ):
-        assert len(running) <= AGX_MAX_ROWS and len(terminal) <= AGX_MAX_ROWS
+        wide = len(running) > AGX_MAX_ROWS or len(terminal) > AGX_MAX_ROWS  # one node type over the row table: both follow the wide rule
+        check_cost_rows(running, "running rows", wide)
+        check_cost_rows(terminal, "terminal rows", wide)
         self.nv = nv
         self.running = list(running)
         self.terminal = list(terminal)

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "agx_traj_cartesian_sine_create", "agx_ocp_set_refs_async", "agx_ocp_refs_activate", "agx_ocp_refs_wait", "agx_host_alloc", "agx_host_free",
     "agx_ocp_download_async", "agx_ocp_download_wait",
     "agx_traj_generic_create_weighted", "agx_traj_cartesian_sine_wi_create", "agx_traj_get_tile",
-    "agx_ocp_set_plant_inertials", "agx_model_sensitivity",
+    "agx_ocp_set_plant_inertials", "agx_model_sensitivity", "agx_ocp_cost_wide",
 ]  # fmt: skip
 
 
@@ -54,13 +54,14 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
     generated front that forwards each call to the group owning the handle.  AGX_BUILD_SPLIT=0 builds
     the single translation unit instead."""
     hdr = _CSRC.parent.parent / "include" / "agimus_hip.h"
-    srcs = [_CSRC / "agimus_hip.hip"] + sorted(_CSRC.glob("*.hpp")) + [hdr, _CSRC / "agx_front.py"]
+    pairs_src = _CSRC / "agx_cost_pairs.hip"  # the wide-cost-set kernels: a translation unit of their own (see the file)
+    srcs = [_CSRC / "agimus_hip.hip"] + sorted(_CSRC.glob("*.hpp")) + [hdr, _CSRC / "agx_front.py", pairs_src]
     if not force and LIB_PATH.exists() and LIB_PATH.stat().st_mtime >= max(s.stat().st_mtime for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
     if os.environ.get("AGX_BUILD_SPLIT", "1") == "0":
-        _run(base + ["-shared", "-o", str(LIB_PATH), str(srcs[0])], verbose)
+        _run(base + [f"-I{hdr.parent}", "-shared", "-o", str(LIB_PATH), str(srcs[0]), str(pairs_src)], verbose)
         return LIB_PATH
     import importlib.util
 
@@ -74,6 +75,8 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
     for g in front.GROUPS:
         cmd = base + ["-c", f"-I{hdr.parent}"] + front.rename_flags(names, g) + ["-o", str(obj / f"agx_g{g}.o"), str(srcs[0])]
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
+    cmd = base + ["-c", f"-I{hdr.parent}", "-DAGX_GROUP=0", "-o", str(obj / "agx_cost_pairs.o"), str(pairs_src)]  # the sizes of group 0
+    procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
     (obj / "agx_front.cpp").write_text(front.front_source(hdr.read_text()))
     _run(["g++", "-O2", "-std=c++17", "-fPIC", f"-I{hdr.parent}", "-c", "-o", str(obj / "agx_front.o"), str(obj / "agx_front.cpp")], verbose)
     failed = None
@@ -86,7 +89,7 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
     if failed:
         raise failed
     _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB_PATH)] + [str(obj / f"agx_g{g}.o") for g in front.GROUPS]
-         + [str(obj / "agx_front.o")], verbose)
+         + [str(obj / "agx_cost_pairs.o"), str(obj / "agx_front.o")], verbose)
     return LIB_PATH
 
 
@@ -185,6 +188,11 @@ class HipOcp:
             L.agx_model_destroy(self._m)
             self._m = None
             raise HipError(msg)
+
+    @property
+    def cost_wide(self) -> bool:
+        """The handle runs a wide cost set (agx_ocp_cost_wide): set_refs then takes no frame-id table."""
+        return lib().agx_ocp_cost_wide(self._h) == 1
 
     def close(self):
         if getattr(self, "_h", None):

@@ -17,6 +17,12 @@
 
 #include "agx_kernels.hpp"
 
+// launchers of the wide-cost-set kernels, compiled in a translation unit of their own (agx_cost_pairs.hip)
+extern "C" int agx_cost_pairs_launch(int dest, void *stream, long long nodes, const DevModel *m, const DevOcp *o, const DevCostWide *w,
+                                     const double *dts, const double *xs, const RefView *rv, double *out, double *auxs, const DevState *st,
+                                     int phase, int sel, int which);
+extern "C" int agx_cost_pairs_fill_launch(void *stream, const DevCostWide *w, const double *gw_item, double *traj, long long units, int stride);
+
 namespace {
 
 thread_local std::string g_err;
@@ -79,6 +85,14 @@ struct agx_ocp {
   bool k1_lanes = true;  // AGX_K1_LANES=0 selects the one-lane-per-node derivative kernel
   bool lanes_ok = true;  // problem fits the LDS staging of the 8-lanes-per-node kernel
   bool lanes_coll = false;  // ... in its variant with one collision cost row
+  // Wide cost set (agx_cost_pairs.hpp): ho.rows hold the non-collision prefix of the caller's row tables, the trailing collision
+  // rows live in hw (k_cost_pairs adds them to the tiles behind every K1 launch).  K1 reads d_ocp_k1, a copy of the description
+  // whose `stride` is the length of the prefix (what it stages in LDS); everybody else d_ocp with the stride of the tile.
+  bool cost_wide = false;
+  DevCostWide hw{};
+  DevCostWide *d_cw = nullptr;
+  DevOcp *d_ocp_k1 = nullptr;  // == d_ocp unless cost_wide
+  int n_rows_all[2] = {0, 0};  // rows of the caller's tables, running / terminal (ho.rows[l].n + hw.lay[l].n)
   bool speculate = true;  // AGX_SPECULATE_GAINS=0: gains sweep only on exit
   bool gains_mfma = true; // AGX_GAINS_MFMA=0: scalar K = M Kw - taux for large models
   bool riccati_mx = true;    // AGX_RICCATI_MX=0: nv <= 7 sweeps on the 8 x 8 lane grid (k_riccati) instead of the MFMA operand layout (k_riccati_mx)
@@ -275,6 +289,29 @@ void fill_rows(const agx_cost_row *rows, int n, int nv, int nvu, DevRows &d) {
   }
 }
 
+// A cost-row table as a wide cost set sees it (include/agimus_hip.h): `n_prefix` rows in front of the trailing block of collision
+// rows; `offender` is the first collision row that is not part of that block (-1: the collision rows are trailing).
+struct CostSplit { int n_other = 0, n_pairs = 0, n_prefix = 0, offender = -1; };
+CostSplit split_cost_rows(const agx_cost_row *rows, int n) {
+  CostSplit s;
+  for (int r = 0; r < n; ++r) (rows[r].kind == AGX_RES_COLLISION ? s.n_pairs : s.n_other)++;
+  s.n_prefix = n;
+  while (s.n_prefix > 0 && rows[s.n_prefix - 1].kind == AGX_RES_COLLISION) --s.n_prefix;
+  for (int r = 0; r < s.n_prefix && s.offender < 0; ++r)
+    if (rows[r].kind == AGX_RES_COLLISION) s.offender = r;
+  return s;
+}
+void fill_cost_pairs(const agx_cost_row *rows, int n, const CostSplit &cs, int nv, DevCostPairs &P) {
+  std::memset(&P, 0, sizeof(P));
+  P.n = n - cs.n_prefix;
+  P.first = cs.n_prefix;
+  for (int r = 0; r < cs.n_prefix; ++r) P.prefix += 1 + agx_row_nref(rows[r].kind, nv) + agx_row_nr(rows[r].kind, nv);
+  for (int p = 0; p < P.n; ++p) {
+    const agx_cost_row &c = rows[cs.n_prefix + p];
+    P.fa[p] = c.frame; P.fb[p] = c.frame_b; P.act[p] = c.activation; P.active[p] = c.active; P.alpha[p] = c.alpha; P.weight[p] = c.weight;
+  }
+}
+
 // component k of a residual of `kind` over nv (capacity) joints -> the caller's component over nvu joints, -1 for a pad joint
 int user_component(int kind, int k, int nv, int nvu, bool is_ref) {
   const bool joint_blocks = kind == AGX_RES_STATE || kind == AGX_RES_CONTROL || (kind == AGX_RES_CONTROL_GRAV && !is_ref);
@@ -435,7 +472,7 @@ int ensure_canonical_tiles(agx_ocp *o) {
   return 0;
 }
 
-int launch_calc_diff(agx_ocp *o, bool masked, bool running_only = false) {
+int launch_calc_diff_rows(agx_ocp *o, bool masked, bool running_only) {
   if (ensure_canonical_tiles(o)) return -1;
   return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
     constexpr int NV = decltype(NVc)::value;
@@ -466,7 +503,7 @@ int launch_calc_diff(agx_ocp *o, bool masked, bool running_only = false) {
 // phase 1: the pass runs at the trial iterates (staging halves of xs / us) of the instances in the line search and leaves
 // their tiles in place of the current ones (k_sqp_head / k_sqp_accept, agx_kernels.hpp); nv <= 7 only.
 // compact (phase 0, eight-lane kernel): every instance inherits its tiles (DevState::carry): a grid over nodes 0, T - 1 and T only.
-int launch_calc_qp(agx_ocp *o, bool running_only = false, bool term_only = false, int phase = 0, bool compact = false) {
+int launch_k1(agx_ocp *o, bool running_only, bool term_only, int phase, bool compact) {
   return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
@@ -491,14 +528,14 @@ int launch_calc_qp(agx_ocp *o, bool running_only = false, bool term_only = false
 #define AGX_LAUNCH_LJ(COLL)                                                                                                              \
   do {                                                                                                                                   \
     if (o->k1_fused && !term_only && !running_only) { /* both node types in one launch */                                                \
-      hipLaunchKernelGGL((agx::k_calc_qp_lj_all<NV, COLL>), dim3(n_run + n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, \
+      hipLaunchKernelGGL((agx::k_calc_qp_lj_all<NV, COLL>), dim3(n_run + n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1, o->d_dt, \
                          xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, n_run, phase, cp);                                         \
     } else {                                                                                                                             \
       if (!term_only)                                                                                                                    \
-        hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, false, COLL>), dim3(n_run), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt,     \
+        hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, false, COLL>), dim3(n_run), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1, o->d_dt,     \
                            xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp);                                              \
       if (!running_only)                                                                                                                 \
-        hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, true, COLL>), dim3(n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt,     \
+        hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, true, COLL>), dim3(n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1, o->d_dt,     \
                            xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp);                                              \
     }                                                                                                                                    \
   } while (0)
@@ -524,6 +561,23 @@ int launch_calc_qp(agx_ocp *o, bool running_only = false, bool term_only = false
     HIPCHK(hipGetLastError());
     return 0;
   });
+}
+
+// The trailing collision rows of a wide cost set (agx_cost_pairs.hpp) on the node grid of the K1 launch in front of it.
+// dest: agx::kPairsToQp (QP / aux tiles, nodes chosen by K1's predicate), kPairsToCanonical (o->d_tiles), kPairsDistance
+// (pair `which` at the running nodes into `dist` [B][T]).  sel: 0 every node, 1 running, 2 terminal.
+int launch_cost_pairs(agx_ocp *o, int dest, int sel, int phase, bool masked = false, int which = 0, double *dist = nullptr);
+
+int launch_calc_diff(agx_ocp *o, bool masked, bool running_only = false) {
+  if (launch_calc_diff_rows(o, masked, running_only)) return -1;
+  return o->cost_wide ? launch_cost_pairs(o, agx::kPairsToCanonical, running_only ? 1 : 0, 0, masked) : 0;
+}
+
+// The derivative pass every caller launches: K1 on the row table, then -- wide cost sets -- k_cost_pairs on the same iterate,
+// phase and nodes.
+int launch_calc_qp(agx_ocp *o, bool running_only = false, bool term_only = false, int phase = 0, bool compact = false) {
+  if (launch_k1(o, running_only, term_only, phase, compact)) return -1;
+  return o->cost_wide ? launch_cost_pairs(o, agx::kPairsToQp, running_only ? 1 : (term_only ? 2 : 0), phase) : 0;
 }
 
 // K2 of large models on `tiles` (k_riccati_blk, agx_big_k2.hpp, which documents forward / gains_pass)
@@ -1120,6 +1174,18 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
   return prof_collect(o);
 }
 
+int launch_cost_pairs(agx_ocp *o, int dest, int sel, int phase, bool masked, int which, double *dist) {
+  if (!o->cost_wide || o->nv != 7 || !o->chain) return fail("wide cost sets run on serial chains of at most 7 joints");  // agx_ocp_create admits nothing else
+  const long long nodes = (long long)o->B * (o->T + 1);
+  const double *xs_in = phase ? o->d_xs + (size_t)o->B * (o->T + 1) * o->nx : o->d_xs;
+  double *out = dest == agx::kPairsToQp ? o->d_qt : (dest == agx::kPairsToCanonical ? o->d_tiles : dist);
+  const DevState *st = dest == agx::kPairsToQp ? o->d_state : ((dest == agx::kPairsToCanonical && masked) ? o->d_state : nullptr);
+  HIPCHK((hipError_t)agx_cost_pairs_launch(dest, (void *)o->stream, nodes, o->d_model, o->d_ocp, o->d_cw, o->d_dt, xs_in, &o->rv, out,
+                                           dest == agx::kPairsToQp ? o->d_aux : nullptr, st, dest == agx::kPairsToQp ? phase : 0,
+                                           dest == agx::kPairsDistance ? 1 : sel, which));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1227,7 +1293,35 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   if (!m || !d || !out) return fail("agx_ocp_create: null argument");
   if (batch < 1) return fail("agx_ocp_create: batch must be positive");
   if (d->horizon < 1) return fail("agx_ocp_create: horizon must be positive");
-  if (d->n_running_rows > AGX_MAX_ROWS || d->n_terminal_rows > AGX_MAX_ROWS) return fail("agx_ocp_create: too many cost rows");
+  if (d->n_running_rows < 0 || d->n_terminal_rows < 0) return fail("agx_ocp_create: negative row count");
+  // Up to AGX_MAX_ROWS rows per node type keep the row table; more make a wide cost set: at most AGX_MAX_ROWS rows that are not
+  // collision rows in front of at most AGX_MAX_COST_PAIRS trailing collision rows, on a serial chain of the 7-joint capacity.
+  // AGX_COST_WIDE=1 gives every set with a collision cost row that layout where it meets these conditions.
+  const CostSplit csplit[2] = {split_cost_rows(d->running_rows, d->n_running_rows), split_cost_rows(d->terminal_rows, d->n_terminal_rows)};
+  bool cost_wide = false;
+  {
+    const bool wide_model = m->h.is_chain && m->h.nv <= 7;
+    if (d->n_running_rows > AGX_MAX_ROWS || d->n_terminal_rows > AGX_MAX_ROWS) {
+      for (int lay = 0; lay < 2; ++lay) {
+        const char *which = lay ? "terminal" : "running";
+        if (csplit[lay].n_other > AGX_MAX_ROWS)
+          return fail(std::string("agx_ocp_create: too many cost rows: at most ") + std::to_string(AGX_MAX_ROWS) + " " + which +
+                      " rows that are not collision rows (AGX_MAX_ROWS)");
+        if (csplit[lay].n_pairs > AGX_MAX_COST_PAIRS)
+          return fail(std::string("agx_ocp_create: too many cost rows: at most ") + std::to_string(AGX_MAX_COST_PAIRS) + " " + which +
+                      " collision-pair cost rows (AGX_MAX_COST_PAIRS)");
+        if (csplit[lay].offender >= 0)
+          return fail(std::string("agx_ocp_create: the collision rows of a wide cost set (more than ") + std::to_string(AGX_MAX_ROWS) +
+                      " cost rows) must be the trailing rows of the table: " + which + " row " + std::to_string(csplit[lay].offender) +
+                      " has other rows behind it");
+      }
+      if (!m->h.is_chain) return fail("agx_ocp_create: a wide cost set (more than " + std::to_string(AGX_MAX_ROWS) + " cost rows per node type) needs a serial chain: trees are not supported");
+      if (m->h.nv > 7) return fail("agx_ocp_create: a wide cost set (more than " + std::to_string(AGX_MAX_ROWS) + " cost rows per node type) is implemented for models of at most 7 joints after padding");
+      cost_wide = true;
+    } else if (const char *e = getenv("AGX_COST_WIDE")) {
+      cost_wide = e[0] == '1' && wide_model && csplit[0].n_pairs + csplit[1].n_pairs > 0 && csplit[0].offender < 0 && csplit[1].offender < 0;
+    }
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("agx_ocp_create: no HIP device available (this library has no CPU path)");
   if (device < 0 || device >= ndev) return fail("agx_ocp_create: bad device index");
@@ -1285,8 +1379,15 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   o->dt.assign(d->dt, d->dt + d->horizon);
   std::memset(&o->ho, 0, sizeof(o->ho));
   o->ho.T = o->T; o->ho.B = o->B; o->ho.stride = o->stride;
-  fill_rows(d->running_rows, d->n_running_rows, o->nv, m->nvu, o->ho.rows[0]);
-  fill_rows(d->terminal_rows, d->n_terminal_rows, o->nv, m->nvu, o->ho.rows[1]);
+  o->cost_wide = cost_wide;
+  o->n_rows_all[0] = d->n_running_rows; o->n_rows_all[1] = d->n_terminal_rows;
+  // wide cost sets: the row table holds the prefix, the pair table the trailing collision rows
+  fill_rows(d->running_rows, cost_wide ? csplit[0].n_prefix : d->n_running_rows, o->nv, m->nvu, o->ho.rows[0]);
+  fill_rows(d->terminal_rows, cost_wide ? csplit[1].n_prefix : d->n_terminal_rows, o->nv, m->nvu, o->ho.rows[1]);
+  if (cost_wide) {
+    fill_cost_pairs(d->running_rows, d->n_running_rows, csplit[0], o->nv, o->hw.lay[0]);
+    fill_cost_pairs(d->terminal_rows, d->n_terminal_rows, csplit[1], o->nv, o->hw.lay[1]);
+  }
   o->ho.tol = d->termination_tolerance;
   o->ho.mu_dyn = d->mu_dynamic;
   o->ho.mu_con = d->mu_constraint;
@@ -1298,23 +1399,25 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
     // blocks of State / Control references and activation weights grow from nvu to nv entries (pad weights 1: the pad
     // residuals are identically zero, the weight only keeps the pad block of the Hessians well conditioned)
     for (int lay = 0; lay < 2; ++lay) {
-      const DevRows &R = o->ho.rows[lay];
+      const agx_cost_row *rows = lay ? d->terminal_rows : d->running_rows;  // every row of the table, the pairs of a wide set included
       o->refmap[lay].assign(o->stride, -1);
       o->reffill[lay].assign(o->stride, 0.0);
-      int off_u = 0;
-      for (int r = 0; r < R.n; ++r) {
-        const int kind = R.kind[r], nref_u = agx_row_nref(kind, o->nvu), nr_u = agx_row_nr(kind, o->nvu);
-        o->refmap[lay][R.off[r]] = off_u;
-        for (int k = 0; k < R.nref[r]; ++k) {
+      int off_u = 0, off = 0;
+      for (int r = 0; r < o->n_rows_all[lay]; ++r) {
+        const int kind = rows[r].kind, nref_u = agx_row_nref(kind, o->nvu), nr_u = agx_row_nr(kind, o->nvu);
+        const int nref = agx_row_nref(kind, o->nv), nr = agx_row_nr(kind, o->nv);
+        o->refmap[lay][off] = off_u;
+        for (int k = 0; k < nref; ++k) {
           const int ku = user_component(kind, k, o->nv, o->nvu, true);
-          o->refmap[lay][R.off[r] + 1 + k] = ku >= 0 ? off_u + 1 + ku : -1;
+          o->refmap[lay][off + 1 + k] = ku >= 0 ? off_u + 1 + ku : -1;
         }
-        for (int k = 0; k < R.nr[r]; ++k) {
+        for (int k = 0; k < nr; ++k) {
           const int ku = user_component(kind, k, o->nv, o->nvu, false);
-          o->refmap[lay][R.off[r] + 1 + R.nref[r] + k] = ku >= 0 ? off_u + 1 + nref_u + ku : -1;
-          if (ku < 0) o->reffill[lay][R.off[r] + 1 + R.nref[r] + k] = 1.0;
+          o->refmap[lay][off + 1 + nref + k] = ku >= 0 ? off_u + 1 + nref_u + ku : -1;
+          if (ku < 0) o->reffill[lay][off + 1 + nref + k] = 1.0;
         }
         off_u += 1 + nref_u + nr_u;
+        off += 1 + nref + nr;
       }
     }
   }
@@ -1389,7 +1492,9 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
     };
     // at most one collision cost row per node type, capsule / sphere / box pair, serial chain: the COLL variant
     o->lanes_coll = n_collision_rows(o->ho.rows[0]) + n_collision_rows(o->ho.rows[1]) > 0;
-    o->lanes_ok = o->stride <= agx::kLjRef && n_frame_rows(o->ho.rows[0]) <= 2 && n_frame_rows(o->ho.rows[1]) <= 2 &&
+    // (a wide cost set: K1 stages the prefix of the tile only, the pairs are k_cost_pairs' business)
+    const int k1_stride = cost_wide ? std::max(1, std::max(o->hw.lay[0].prefix, o->hw.lay[1].prefix)) : o->stride;
+    o->lanes_ok = k1_stride <= agx::kLjRef && n_frame_rows(o->ho.rows[0]) <= 2 && n_frame_rows(o->ho.rows[1]) <= 2 &&
                   n_collision_rows(o->ho.rows[0]) <= 1 && n_collision_rows(o->ho.rows[1]) <= 1 && !o->general && !n_vector_exp_rows();
   }
   if (o->nv > 8) {
@@ -1409,9 +1514,12 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   // nor a segment's zero-terminal one, whose pivots are the smaller ones -- can meet a non-positive pivot.  An Exp / QuadExp cost
   // row has negative curvature inside its bell: such problems keep the one-wave sweep and its breakdown handling.
   bool convex_rows = true;
-  for (int lay = 0; lay < 2; ++lay)
+  for (int lay = 0; lay < 2; ++lay) {
     for (int r = 0; r < o->ho.rows[lay].n; ++r)
       if (o->ho.rows[lay].active[r] && o->ho.rows[lay].act[r] != AGX_ACT_WEIGHTED_QUAD) convex_rows = false;
+    for (int p = 0; p < o->hw.lay[lay].n; ++p)  // (wide cost sets: the pairs)
+      if (o->hw.lay[lay].active[p] && o->hw.lay[lay].act[p] != AGX_ACT_WEIGHTED_QUAD) convex_rows = false;
+  }
   if (o->nv <= 7 && o->riccati_mx && !o->has_con && convex_rows) {
     // ten segments while the two sweeps of a paired launch (2 B S waves of 254 VGPRs) fit the 2 048 wave slots of the chip
     // at two per SIMD; fewer above that; below five segments the 2.4 x arithmetic is not paid back (measured, B = 256: none)
@@ -1425,7 +1533,8 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   {
     bool one_dt = true;  // nodes with dt_i != dt_0 are re-integrated by the warm-start shift: not the old node's inputs
     for (int t = 0; t < o->T; ++t) one_dt = one_dt && o->dt[t] == o->dt[0];
-    o->carry_static = o->tile_carry && o->nv <= 7 && o->chain && o->k1_lanes && o->lanes_ok && o->riccati_mx && !o->has_con && !o->general && one_dt;
+    o->carry_static = o->tile_carry && o->nv <= 7 && o->chain && o->k1_lanes && o->lanes_ok && o->riccati_mx && !o->has_con && !o->general && one_dt &&
+                      !o->cost_wide;  // (a wide cost set does not carry tiles: k_cost_pairs adds to the tiles of the pass in front of it)
   }
   // probe that a kernel instantiation exists
   if (dispatch(o->nv, o->chain, [](auto, auto) -> int { return 0; })) { delete o; return -1; }
@@ -1438,7 +1547,9 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
     (void)hipMemset((ptr), 0, sizeof(*(ptr)) * (count));                                                   \
   } while (0)
   ALLOC(o->d_model, 1);
-  ALLOC(o->d_ocp, 1);
+  ALLOC(o->d_ocp, o->cost_wide ? 2 : 1);  // wide cost sets: [1] the copy K1 reads
+  o->d_ocp_k1 = o->d_ocp;
+  if (o->cost_wide) ALLOC(o->d_cw, 1);
   ALLOC(o->d_dt, T);
   ALLOC(o->d_xs, 2 * B * (T + 1) * nx);  // second half: shift staging
   ALLOC(o->d_us, 2 * B * T * nu);
@@ -1493,9 +1604,16 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   if (const char *e = getenv("AGX_HOST_POLL")) o->poll = o->poll && (e[0] != '0');
   if (hipMemcpy(o->d_model, &o->hm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(o->d_ocp, &o->ho, sizeof(DevOcp), hipMemcpyHostToDevice) != hipSuccess ||
+      (o->cost_wide && hipMemcpy(o->d_cw, &o->hw, sizeof(DevCostWide), hipMemcpyHostToDevice) != hipSuccess) ||
       hipMemcpy(o->d_dt, o->dt.data(), sizeof(double) * T, hipMemcpyHostToDevice) != hipSuccess) {
     agx_ocp_destroy(o);
     return fail("agx_ocp_create: upload of the problem description failed");
+  }
+  if (o->cost_wide) {
+    DevOcp k1 = o->ho;
+    k1.stride = std::max(1, std::max(o->hw.lay[0].prefix, o->hw.lay[1].prefix));
+    o->d_ocp_k1 = o->d_ocp + 1;
+    if (hipMemcpy(o->d_ocp_k1, &k1, sizeof(DevOcp), hipMemcpyHostToDevice) != hipSuccess) { agx_ocp_destroy(o); return fail("agx_ocp_create: upload of the problem description failed"); }
   }
   if (hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking) != hipSuccess) { agx_ocp_destroy(o); return fail("hipStreamCreate failed"); }
   o->own_stream = true;
@@ -1519,7 +1637,7 @@ void agx_ocp_destroy(agx_ocp *o) {
   if (o->copy_stream) (void)hipStreamSynchronize(o->copy_stream);
   void *ptrs[] = {o->d_mx2_elem, o->d_mx2_bnd, o->d_mx2_cl, o->d_ref_back, o->d_frames_back, o->d_snap, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us, o->d_x0, o->d_tiles, o->d_Kws, o->d_kws, o->d_Kout, o->d_dx,
                   o->d_du, o->d_ref, o->d_frames, o->d_state, o->d_ndone, o->d_scratch, o->d_traj, o->d_pts, o->d_sine, o->d_qt, o->d_aux, o->d_w, o->d_nodestat,
-                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr, o->d_plant};
+                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr, o->d_plant, o->d_cw};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (o->h_ndone) (void)hipHostFree(o->h_ndone);
@@ -1590,8 +1708,14 @@ int agx_ocp_set_geom_placement(agx_ocp *o, int frame, const double *se3) {
   return 0;
 }
 
+int agx_ocp_cost_wide(agx_ocp *o) {
+  if (!o) return fail("null handle");
+  return o->cost_wide ? 1 : 0;
+}
+
 int agx_ocp_set_refs(agx_ocp *o, const double *ref_tile, const int32_t *frame_ids) {
   if (!o || !ref_tile) return fail("agx_ocp_set_refs: null argument");
+  if (frame_ids && o->cost_wide) return fail("agx_ocp_set_refs: a wide cost set takes no frame-id table (rows from AGX_MAX_ROWS on have no column in it)");
   if (set_device(o)) return -1;
   if (carry_invalidate(o)) return -1;
   if (frame_ids) o->frames_uniform = false;
@@ -1615,6 +1739,7 @@ int agx_ocp_set_refs(agx_ocp *o, const double *ref_tile, const int32_t *frame_id
 
 int agx_ocp_set_refs_device(agx_ocp *o, const double *d_ref_tile, const int32_t *d_frame_ids, int adopt) {
   if (!o || !d_ref_tile) return fail("agx_ocp_set_refs_device: null argument");
+  if (d_frame_ids && o->cost_wide) return fail("agx_ocp_set_refs_device: a wide cost set takes no frame-id table (rows from AGX_MAX_ROWS on have no column in it)");
   if (set_device(o)) return -1;
   if (carry_invalidate(o)) return -1;
   if (d_frame_ids) o->frames_uniform = false;
@@ -1657,6 +1782,7 @@ int agx_host_free(void *p) {
 
 int agx_ocp_set_refs_async(agx_ocp *o, const double *ref_tile, const int32_t *frame_ids) {
   if (!o || !ref_tile) return fail("agx_ocp_set_refs_async: null argument");
+  if (frame_ids && o->cost_wide) return fail("agx_ocp_set_refs_async: a wide cost set takes no frame-id table (rows from AGX_MAX_ROWS on have no column in it)");
   if (set_device(o)) return -1;
   if (carry_invalidate(o)) return -1;
   if (ensure_copy_stream(o)) return -1;
@@ -1977,8 +2103,17 @@ int agx_model_frame_jacobian(agx_ocp *o, int n, int frame, int local, const doub
 
 int agx_ocp_get_residuals(agx_ocp *o, int row, double *out) {
   if (!o || !out) return fail("agx_ocp_get_residuals: null argument");
-  if (row < 0 || row >= o->ho.rows[0].n) return fail("agx_ocp_get_residuals: row out of range");
+  if (row < 0 || row >= o->n_rows_all[0]) return fail("agx_ocp_get_residuals: row out of range");
   if (set_device(o)) return -1;
+  if (row >= o->ho.rows[0].n) {  // a pair row of a wide cost set: its distance, one component
+    const size_t cnt = (size_t)o->B * o->T;
+    if (ensure_scratch(o, sizeof(double) * cnt)) return -1;
+    HIPCHK(hipMemsetAsync(o->d_scratch, 0, sizeof(double) * cnt, o->stream));  // (an inactive row is not evaluated)
+    if (launch_cost_pairs(o, agx::kPairsDistance, 1, 0, false, row - o->hw.lay[0].first, o->d_scratch)) return -1;
+    HIPCHK(hipMemcpyAsync(out, o->d_scratch, sizeof(double) * cnt, hipMemcpyDeviceToHost, o->stream));
+    HIPCHK(hipStreamSynchronize(o->stream));
+    return 0;
+  }
   const int nr = o->ho.rows[0].nr[row];
   const size_t cnt = (size_t)o->B * o->T * nr;
   if (ensure_scratch(o, sizeof(double) * cnt)) return -1;
@@ -2095,7 +2230,7 @@ int agx_ocp_time_kernel(agx_ocp *o, int which, int reps, double *avg_ms) {
   // state for the timed kernel: fresh solver state, QP tiles and a direction at the resident point
   if (carry_invalidate(o)) return -1;
   if (reset_state(o)) return -1;
-  if (which == 1 || which == 2 || which == 5 || which == 6 || which == 7) { if (launch_calc_qp(o)) return -1; }
+  if (which == 1 || which == 2 || which == 5 || which == 6 || which == 7 || which == 9) { if (launch_calc_qp(o)) return -1; }
   if (which == 2) { if (launch_riccati(o, 1, 0)) return -1; }
   double *d_x0_keep = nullptr;
   if (which == 8) {  // every rollout moves x0: the timed ones start from where the last one ended, the caller's x0 comes back afterwards
@@ -2118,6 +2253,7 @@ int agx_ocp_time_kernel(agx_ocp *o, int which, int reps, double *avg_ms) {
       else if (which == 6) rc = launch_gains(o);
       else if (which == 7) rc = launch_riccati(o, 1, true, 1);
       else if (which == 8) rc = launch_rollout(o, 10, 1e-3, nullptr);
+      else if (which == 9) rc = o->cost_wide ? launch_cost_pairs(o, agx::kPairsToQp, 0, 0) : fail("agx_ocp_time_kernel: kernel 9 (k_cost_pairs) needs a wide cost set");
       else return fail("agx_ocp_time_kernel: unknown kernel");
       if (rc) return rc;
     }
@@ -2142,6 +2278,15 @@ int agx_ocp_profile(agx_ocp *o, int enable, double *ms_sum, long long *count) {
     o->prof = enable != 0;
     for (int k = 0; k < 3; ++k) { o->prof_ms[k] = 0.0; o->prof_n[k] = 0; }
   }
+  return 0;
+}
+
+// Wide cost sets: k_sine_fill has written the rows of the prefix; the pair rows of every sample get [row.weight (or the scheduled
+// item weight gw_item [B][n_points], device) | 1].
+static int traj_fill_pairs(agx_ocp *o, const double *d_gw_item) {
+  if (!o->cost_wide) return 0;
+  const long long units = (long long)o->B * o->n_points;
+  HIPCHK((hipError_t)agx_cost_pairs_fill_launch((void *)o->stream, o->d_cw, d_gw_item, o->d_traj, units, o->stride));
   return 0;
 }
 
@@ -2202,6 +2347,7 @@ int agx_traj_sine_create(agx_ocp *o, int n_points, double dt, const double *q0, 
     return 0;
   });
   if (rc) return rc;
+  if (traj_fill_pairs(o, sp.gw_item)) return -1;
   HIPCHK(hipStreamSynchronize(o->stream));
   if (traj_frames(o, frame)) return -1;
   return agx_traj_set_window(o, 0);
@@ -2261,6 +2407,7 @@ static int traj_generic_build(agx_ocp *o, const char *fn, int n_points, const do
     return 0;
   });
   if (rc) return rc;
+  if (traj_fill_pairs(o, sp.gw_item)) return -1;
   HIPCHK(hipStreamSynchronize(o->stream));
   if (traj_frames(o, frame)) return -1;
   return agx_traj_set_window(o, 0);
@@ -2349,6 +2496,7 @@ static int traj_cartesian_build(agx_ocp *o, const char *fn, int n_points, double
     return 0;
   });
   if (rc) return rc;
+  if (traj_fill_pairs(o, sp.gw_item)) return -1;
   std::vector<int> failed(B);
   HIPCHK(hipMemcpyAsync(failed.data(), dfail, sizeof(int) * B, hipMemcpyDeviceToHost, o->stream));
   HIPCHK(hipStreamSynchronize(o->stream));
@@ -2464,7 +2612,7 @@ int agx_traj_get_tile(agx_ocp *o, int k, int terminal, double *out) {
   HIPCHK(hipStreamSynchronize(o->stream));
   // the generators write the rows of the layout; what lies behind them in a slot of `stride` doubles is returned as zeros
   const DevRows &R = o->ho.rows[lay];
-  const size_t used = R.n ? (size_t)R.off[R.n - 1] + 1 + R.nref[R.n - 1] + R.nr[R.n - 1] : 0;
+  const size_t used = (R.n ? (size_t)R.off[R.n - 1] + 1 + R.nref[R.n - 1] + R.nr[R.n - 1] : 0) + 2 * (size_t)o->hw.lay[lay].n;  // + the pair rows of a wide cost set
   std::memset(out, 0, sizeof(double) * B * su);
   for (size_t b = 0; b < B; ++b)
     for (size_t e = 0; e < used; ++e) {

@@ -1,0 +1,28 @@
+// agx_cost_pairs.hip -- translation unit of the wide-cost-set kernels (agx_cost_pairs.hpp), linked into libagimus_hip.so next
+// to the per-capacity units of agimus_hip.hip, which call the two launchers below.
+#include <hip/hip_runtime.h>
+
+#include "agx_cost_pairs.hpp"
+
+extern "C" {
+
+// k_cost_pairs<7, dest> on a grid of 8 lanes per node; returns the hipError_t of the launch
+int agx_cost_pairs_launch(int dest, void *stream, long long nodes, const DevModel *m, const DevOcp *o, const DevCostWide *w, const double *dts,
+                          const double *xs, const RefView *rv, double *out, double *auxs, const DevState *st, int phase, int sel, int which) {
+  const dim3 grid((unsigned)((nodes * 8 + 63) / 64)), blk(64);
+  hipStream_t s = (hipStream_t)stream;
+  if (dest == agx::kPairsToQp)
+    hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsToQp>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which);
+  else if (dest == agx::kPairsToCanonical)
+    hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsToCanonical>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which);
+  else
+    hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsDistance>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which);
+  return (int)hipGetLastError();
+}
+
+int agx_cost_pairs_fill_launch(void *stream, const DevCostWide *w, const double *gw_item, double *traj, long long units, int stride) {
+  hipLaunchKernelGGL(agx::k_cost_pairs_fill, dim3((unsigned)((units * 2 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, gw_item, traj, units, stride);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

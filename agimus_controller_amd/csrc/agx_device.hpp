@@ -84,6 +84,20 @@ struct DevCons {
   double plb[AGX_MAX_PAIRS], pub[AGX_MAX_PAIRS];      // bounds of pair p
 };
 
+// Wide cost sets (agx_cost_pairs.hpp): the trailing collision cost rows of a node type, next to DevOcp::rows (the prefix).
+// The pair table of one node type: pair p is row `first + p` of the caller's table and owns [item weight | activation weight] at
+// reference-tile offset `prefix + 2 p`.
+struct DevCostPairs {
+  int n, prefix;  // pairs; reference-tile doubles of the non-collision rows in front of them
+  int first, pad;
+  int fa[AGX_MAX_COST_PAIRS], fb[AGX_MAX_COST_PAIRS];  // geometry frames of pair p
+  int act[AGX_MAX_COST_PAIRS], active[AGX_MAX_COST_PAIRS];
+  double alpha[AGX_MAX_COST_PAIRS], weight[AGX_MAX_COST_PAIRS];
+};
+struct DevCostWide {
+  DevCostPairs lay[2];  // 0 running, 1 terminal
+};
+
 struct DevOcp {
   int T, B, stride;
   int head;  // ring origin of the running-node tiles (tile_slot, agx_kernels.hpp); 0 wherever tiles are not carried across MPC steps

@@ -134,7 +134,7 @@ __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds
   const int b = TERM ? (int)nid : (int)(nid / n_per), tn = TERM ? 0 : (int)(nid % n_per);
   const int t = TERM ? T : ((compact && tn) ? T - 1 : tn);
   // phase 1: the trial points of the instances in the line search; carry: every other running node keeps the tile it has
-  const bool act = node_ok && k1_active(st[b], phase) && (TERM || !st[b].carry || t == 0 || t == T - 1);
+  const bool act = node_ok && k1_node_active(st[b], phase, TERM, t, T);
   if (!__any(act)) return;  // the whole wave (= workgroup) belongs to instances this pass skips
   const bool jl = l8 < NV;       // lane carries a joint
   const int j = jl ? l8 : NV - 1;

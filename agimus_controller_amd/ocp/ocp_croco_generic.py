@@ -593,8 +593,6 @@ class DifferentialActionModelFreeFwdDynamics(DifferentialActionModel):
 
     def lower(self, data: BuildData) -> list[_abi.RowSpec]:
         """Cost items -> row table (the counterpart of building a crocoddyl.CostModelSum)."""
-        if len(self.costs) > _abi.AGX_MAX_ROWS:
-            raise ValueError(f"at most {_abi.AGX_MAX_ROWS} cost items per node are supported")
         rows = []
         for item in self.costs:
             res, act = item.cost.residual, item.cost.activation
@@ -611,6 +609,8 @@ class DifferentialActionModelFreeFwdDynamics(DifferentialActionModel):
             frame_b = res.reference_frame_id() if kind == _abi.RES_FRAME_VELOCITY else 0
             rows.append(_abi.RowSpec(kind=kind, activation=act_kind, active=bool(item.active), frame=res.frame(data),
                                      frame_b=frame_b, alpha=alpha, name=item.name, weight=float(item.weight)))  # fmt: skip
+        # at most 8 items, or a wide cost set: at most 8 items that are not collision pairs, then up to 64 collision pairs, last
+        _abi.check_cost_rows(rows, "cost items of a node")
         return rows
 
 
@@ -691,7 +691,24 @@ class OCPCrocoGeneric(OCPBaseCroco):
                 ref[...] = item.cost.residual.reference(self._build_data_obj)
                 nr = aw.shape[-1]
                 aw[...] = np.ones(nr) if item.cost.activation is None else item.cost.activation.initial_weights(nr)
-        self._hip.set_refs(self._ref_tile, self._frames)
+        self._hip.set_refs(self._ref_tile, self._frames_for_device())
+
+    def _frames_for_device(self):
+        """The frame-id table set_refs gets.  A handle with a wide cost set takes none (the rows from AGX_MAX_ROWS on have no
+        column in it): every frame row then looks at the frame of its cost item on every node, and a trajectory point that asks
+        for another frame is refused here."""
+        if not self._hip.cost_wide:
+            return self._frames
+        T_ = self._packed.horizon
+        for terminal, rows in ((False, self._running_rows), (True, self._terminal_rows)):
+            ids = self._frames[0, T_:, :] if terminal else self._frames[0, :T_, :]
+            for row, spec in enumerate(rows[: _abi.AGX_MAX_ROWS]):
+                other = ids[:, row][(ids[:, row] >= 0) & (ids[:, row] != spec.frame)]
+                if other.size:
+                    raise ValueError(f"cost '{spec.name}': frame id {int(other[0])} differs from the item's own frame {spec.frame}; "
+                                     f"with more than {_abi.AGX_MAX_ROWS} cost items (or AGX_COST_WIDE=1) per-node frame ids are not supported: "
+                                     f"give the item that frame as its `id`")
+        return None
 
     def _update_node(self, terminal: bool, node: int, pt: WeightedTrajectoryPoint):
         po = self._packed
@@ -727,7 +744,7 @@ class OCPCrocoGeneric(OCPBaseCroco):
                 self._update_node(False, node, pt)
             self._first_call = False
         self._update_node(True, T_, reference_weighted_trajectory[-1])
-        self._hip.set_refs(self._ref_tile, self._frames)
+        self._hip.set_refs(self._ref_tile, self._frames_for_device())
 
     # -- debug data -----------------------------------------------------------
     def init_debug_data_attributes(self) -> None:

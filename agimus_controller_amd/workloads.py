@@ -60,6 +60,19 @@ def collision_pair_constraints(table, pairs, lower, upper=np.inf):
                                 name=f"collision_{i}") for i, (a, b) in enumerate(pairs)]
 
 
+def collision_pair_costs(table, pairs, activation=_abi.ACT_QUAD_EXP, alpha=0.05, weight=1.0):
+    """Cost rows weight * activation(distance(a, b)) of the CostModelResidual items on ResidualDistanceCollision
+    (ocp_croco_generic.py:524-533 upstream), one per geometry pair (a, b) of `pairs` (frame names or ids).  alpha / weight: one
+    value for every pair or one per pair.  Append them BEHIND the other rows of a node type: up to 64 of them next to up to 8
+    other rows run on the device (wide cost sets)."""
+    pairs = list(pairs)
+    al = np.broadcast_to(np.asarray(alpha, dtype=float), (len(pairs),))
+    we = np.broadcast_to(np.asarray(weight, dtype=float), (len(pairs),))
+    fid = lambda f: f if isinstance(f, (int, np.integer)) else table.frame_id(f)  # noqa: E731
+    return [_abi.RowSpec(_abi.RES_COLLISION, activation=int(activation), frame=int(fid(a)), frame_b=int(fid(b)), alpha=float(al[i]),
+                         weight=float(we[i]), name=f"collision_cost_{i}") for i, (a, b) in enumerate(pairs)]
+
+
 # link capsules of robot_tables.panda_collision_table and four pairs of them that do not touch in normal postures
 PANDA_LINK_CAPSULES = ["panda_link2_capsule_0", "panda_link3_capsule_0", "panda_link4_capsule_0", "panda_link5_capsule_0",
                        "panda_link7_capsule_0"]

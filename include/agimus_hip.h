@@ -31,7 +31,14 @@
 extern "C" {
 #endif
 
-#define AGX_MAX_ROWS 8   /* cost rows per node type (running / terminal)        */
+#define AGX_MAX_ROWS 8   /* cost rows per node type (running / terminal) that are not collision rows of a wide cost set */
+/* Wide cost sets (serial chains of at most 7 joints after padding): a node type may carry up to AGX_MAX_ROWS rows of any kind
+ * followed by up to AGX_MAX_COST_PAIRS AGX_RES_COLLISION rows (soft collision avoidance, one row per collision pair).  The
+ * rows stay plain agx_cost_row entries in table order and every collision row owns [item weight | activation weight] at its
+ * table offset of the reference tile.  A set is wide when a node type has more than AGX_MAX_ROWS rows (AGX_COST_WIDE=1: any
+ * set with a collision cost row that meets the conditions); its collision rows must be the trailing rows of the table, and
+ * the handle takes no frame-id table (rows >= AGX_MAX_ROWS have no column in it).  Kernel: k_cost_pairs.                  */
+#define AGX_MAX_COST_PAIRS 64
 #define AGX_MAX_NV 32    /* joints a model table may have; kernels are compiled for nv in {1,2,3,4,6,7} (register-resident
                             path) and 30 (LDS path for large models); other sizes are refused by agx_ocp_create */
 
@@ -209,6 +216,10 @@ int agx_ocp_reset_duals(agx_ocp *ocp);
  * (ocp_croco_generic.py:855-892): ref_tile [B][T+1][stride] host doubles,
  * frame_ids [B][T+1][AGX_MAX_ROWS] host int32 (NULL = row defaults).            */
 int agx_ocp_set_refs(agx_ocp *ocp, const double *ref_tile, const int32_t *frame_ids);
+/* 1 when the handle runs a wide cost set (more than AGX_MAX_ROWS cost rows in a node type, or AGX_COST_WIDE=1 on a set that
+ * qualifies), 0 otherwise.  On such a handle agx_ocp_set_refs, agx_ocp_set_refs_async and agx_ocp_set_refs_device refuse a
+ * non-NULL frame-id table: every frame row looks at the frame of its agx_cost_row on every node.                           */
+int agx_ocp_cost_wide(agx_ocp *ocp);
 /* The same update without stalling the caller or the solver (the reference pays ~ T x #costs binding calls per step for it,
  * ocp_croco_generic.py:883-888), in two halves so that the tile of step k+1 can travel while step k is being solved:
  *   agx_ocp_set_refs_async  STAGES a tile: a second stream copies it into the handle's second device tile (the solver
@@ -293,7 +304,7 @@ int agx_model_sensitivity(agx_ocp *ocp, int n, double dt, const double *x, const
 
 /* Replaces the per-node residual copies of OCPCrocoGeneric.fill_debug_data
  * (ocp_croco_generic.py:840-853): residual of running row `row` at the resident
- * solution, out [B][T][nr].                                                    */
+ * solution, out [B][T][nr] (a collision row, the pair rows of a wide cost set included: the distance). */
 int agx_ocp_get_residuals(agx_ocp *ocp, int row, double *out);
 
 /* ---- kernel-level entry points (parity tests and bench instrumentation) - */
@@ -317,7 +328,8 @@ int agx_ocp_qp_tiles(agx_ocp *ocp, double *qt, double *aux, int *qt_size, int *a
  * nodes only (one launch), 4 = canonical-tile derivative pass (running nodes), 5 = Riccati backward
  * only, 6 = exit (gains) sweep alone, 7 = direction + speculative gains sweep in one launch,
  * 8 = the closed-loop rollout of agx_ocp_feedback_rollout as the handle would launch it (10 sub-steps of
- * 1 ms, no disturbance; with or without a plant), x0 restored afterwards.                          */
+ * 1 ms, no disturbance; with or without a plant), x0 restored afterwards, 9 = k_cost_pairs alone (wide cost sets; on
+ * such a handle 0 and 3 time K1 and k_cost_pairs together, as every derivative pass launches them).             */
 int agx_ocp_time_kernel(agx_ocp *ocp, int which, int reps, double *avg_ms);
 
 /* In-situ kernel timing: while enabled, every solve brackets the launches of its SQP loop with
