@@ -78,6 +78,7 @@ class ModelDesc(C.Structure):
         ("frame_radius", c_double_p),
         ("frame_halflen", c_double_p),
         ("frame_box", c_double_p),
+        ("joint_type", c_int32_p),
     ]
 
 
@@ -284,6 +285,8 @@ class PackedModel:
         self.frame_halflen = f8(np.zeros(self.nframes) if hl is None else hl, (self.nframes,))
         bx = getattr(table, "frame_box", None)
         self.frame_box = f8(np.zeros((self.nframes, 3)) if bx is None else bx, (self.nframes, 3))
+        jt = getattr(table, "joint_type", None)  # None: a NULL pointer, all joints revolute
+        self.joint_type = None if jt is None else np.ascontiguousarray(np.asarray(jt, dtype=np.int32).reshape(nv))
         d = ModelDesc()
         d.nv = nv
         d.nframes = self.nframes
@@ -301,6 +304,8 @@ class PackedModel:
         d.frame_radius = _dptr(self.frame_radius)
         d.frame_halflen = _dptr(self.frame_halflen)
         d.frame_box = _dptr(self.frame_box)
+        if self.joint_type is not None:
+            d.joint_type = _iptr(self.joint_type)
         self.desc = d
 
 

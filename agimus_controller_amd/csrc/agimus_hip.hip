@@ -451,6 +451,14 @@ int pad_capacity(int nv) {
   return best;
 }
 
+// The workgroup-per-node kernels are instantiated with and without the prismatic-joint code (agx_big_k1.hpp: PRISM): a model
+// without a prismatic joint runs the instruction stream of the revolute-only kernels.  f(std::bool_constant<PRISM>) launches.
+template <typename F>
+void launch_wg(const agx_ocp *o, F &&f) {
+  if (o->hm.prismatic) f(std::true_type());
+  else f(std::false_type());
+}
+
 template <typename F>
 int dispatch(int nv, bool chain, F &&f) {
   switch (nv) {
@@ -548,8 +556,10 @@ int launch_k1(agx_ocp *o, bool running_only, bool term_only, int phase, bool com
       // large models: one workgroup per node, running and terminal nodes in one launch (agx_big_k1.hpp)
       (void)lanes; (void)running_only;
       if (term_only) return 0;  // the launch of the running nodes (profiled path) already covered the terminal ones
-      hipLaunchKernelGGL((agx::k_calc_qp_wg<NV>), dim3((int)(units + o->B)), dim3(256), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, xs_in,
+      launch_wg(o, [&](auto PRc) {
+        hipLaunchKernelGGL((agx::k_calc_qp_wg<NV, decltype(PRc)::value>), dim3((int)(units + o->B)), dim3(256), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, xs_in,
                          us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase);
+      });
     } else if (!lanes) {
       if (!term_only)
         hipLaunchKernelGGL((agx::k_calc_qp<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
@@ -946,8 +956,10 @@ int admm_direction(agx_ocp *o, bool prefactor = false) {
       if (launch_step(o, 0, 0, 0, true, false)) return -1;  // du of the initial guess (k_node_kkt_big)
       HIPCHK(hipMemsetAsync(o->d_ndone + 1, 0, sizeof(int), o->stream));
       hipLaunchKernelGGL((agx::k_admm_init<NV>), dim3(g1), dim3(256), 0, o->stream, o->d_ocp, o->d_dx, o->d_cx, o->d_z, o->d_state, o->d_ndone + 1);
-      hipLaunchKernelGGL((agx::k_con_eval_wg<NV>), dim3((int)nodes), dim3(256), 0, o->stream, o->d_model, o->d_ocp, o->d_xs, o->d_us, o->d_cg, o->d_cjac,
+      launch_wg(o, [&](auto PRc) {
+        hipLaunchKernelGGL((agx::k_con_eval_wg<NV, decltype(PRc)::value>), dim3((int)nodes), dim3(256), 0, o->stream, o->d_model, o->d_ocp, o->d_xs, o->d_us, o->d_cg, o->d_cjac,
                          o->d_nodestat, o->d_state, 0);
+      });
       HIPCHK(hipGetLastError());
       const int max_qp = o->ho.max_qp;
       for (int iter = 1; iter <= max_qp; ++iter) {
@@ -1046,8 +1058,10 @@ int line_search_rounds(agx_ocp *o, int it, int max_iter, bool *need_k1, int *n_d
       }
       if constexpr (NV > 7) if (o->has_con) {
         const long long nodes = (long long)o->B * (o->T + 1);
-        hipLaunchKernelGGL((agx::k_con_eval_wg<NV>), dim3((int)nodes), dim3(256), 0, o->stream, o->d_model, o->d_ocp, xs_t, us_t, o->d_cg, o->d_cjac,
+        launch_wg(o, [&](auto PRc) {
+        hipLaunchKernelGGL((agx::k_con_eval_wg<NV, decltype(PRc)::value>), dim3((int)nodes), dim3(256), 0, o->stream, o->d_model, o->d_ocp, xs_t, us_t, o->d_cg, o->d_cjac,
                            o->d_nodestat, o->d_state, 1);
+      });
       }
       if (prof_mark(o, 2, true)) return -1;
       hipLaunchKernelGGL((agx::k_sqp_accept<NV>), dim3(o->B), dim3(128), 0, o->stream, o->d_ocp, o->d_xs, o->d_us, o->d_dx, o->d_du, xs_t, us_t,
@@ -1175,7 +1189,7 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
 }
 
 int launch_cost_pairs(agx_ocp *o, int dest, int sel, int phase, bool masked, int which, double *dist) {
-  if (!o->cost_wide || o->nv != 7 || !o->chain) return fail("wide cost sets run on serial chains of at most 7 joints");  // agx_ocp_create admits nothing else
+  if (!o->cost_wide || o->nv != 7 || !o->chain) return fail("wide cost sets run on serial chains of revolute joints, at most 7 of them");  // agx_ocp_create admits nothing else
   const long long nodes = (long long)o->B * (o->T + 1);
   const double *xs_in = phase ? o->d_xs + (size_t)o->B * (o->T + 1) * o->nx : o->d_xs;
   double *out = dest == agx::kPairsToQp ? o->d_qt : (dest == agx::kPairsToCanonical ? o->d_tiles : dist);
@@ -1257,9 +1271,19 @@ int agx_model_create(const agx_model_desc *d, agx_model **out) {
     std::memcpy(h.com[i], d->com + 3 * i, sizeof(double) * 3);
     std::memcpy(h.inertia[i], d->inertia + 9 * i, sizeof(double) * 9);
     h.armature[i] = d->armature ? d->armature[i] : 0.0;
+    const int jt = d->joint_type ? d->joint_type[i] : AGX_JOINT_REVOLUTE;
+    if (jt != AGX_JOINT_REVOLUTE && jt != AGX_JOINT_PRISMATIC) {
+      delete m;
+      return fail("agx_model_create: joint " + std::to_string(i) + " has joint_type " + std::to_string(jt) + ": 0 (revolute) and 1 (prismatic) are supported");
+    }
+    if (jt == AGX_JOINT_PRISMATIC) h.prismatic |= 1u << i;
   }
+  // The eight-lane kernels, wide cost / constraint sets and the tile carry are written for serial chains of revolute joints: a model
+  // with a prismatic joint takes the kernels (and the padding) of a tree of its size, which know both joint types.
+  if (h.prismatic) h.is_chain = 0;
   // pad joints (robot_model.py:231-257 takes any URDF and any set of locked joints; the kernels come in a few capacities): massless,
-  // unit armature, identity placement -- appended to a serial chain (the eight-lane kernel needs one), children of the universe in a tree
+  // unit armature, identity placement, revolute -- appended to a serial chain of revolute joints (the eight-lane kernel needs one), children
+  // of the universe otherwise
   for (int i = d->nv; i < cap; ++i) {
     h.parent[i] = h.is_chain ? i - 1 : -1;
     h.anc[i] = (1u << i) | (h.parent[i] >= 0 ? h.anc[h.parent[i]] : 0u);
@@ -1315,7 +1339,7 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
                       " cost rows) must be the trailing rows of the table: " + which + " row " + std::to_string(csplit[lay].offender) +
                       " has other rows behind it");
       }
-      if (!m->h.is_chain) return fail("agx_ocp_create: a wide cost set (more than " + std::to_string(AGX_MAX_ROWS) + " cost rows per node type) needs a serial chain: trees are not supported");
+      if (!m->h.is_chain) return fail("agx_ocp_create: a wide cost set (more than " + std::to_string(AGX_MAX_ROWS) + " cost rows per node type) needs a serial chain of revolute joints: trees and models with prismatic joints are not supported");
       if (m->h.nv > 7) return fail("agx_ocp_create: a wide cost set (more than " + std::to_string(AGX_MAX_ROWS) + " cost rows per node type) is implemented for models of at most 7 joints after padding");
       cost_wide = true;
     } else if (const char *e = getenv("AGX_COST_WIDE")) {
@@ -1998,8 +2022,10 @@ int agx_ocp_shift_warmstart(agx_ocp *o) {
       (void)units;
       hipLaunchKernelGGL(agx::k_shift_copy, dim3((int)((n + 255) / 256)), dim3(256), 0, o->stream, o->d_dt, o->d_xs, o->d_us, o->B, o->T, o->nx, o->nu);
       if (!o->shift_nodes.empty())
-        hipLaunchKernelGGL((agx::k_integrate_wg<NV>), dim3(o->B * (int)o->shift_nodes.size()), dim3(256), 0, o->stream, o->d_model, o->dt[0], o->d_xs,
+        launch_wg(o, [&](auto PRc) {
+        hipLaunchKernelGGL((agx::k_integrate_wg<NV, decltype(PRc)::value>), dim3(o->B * (int)o->shift_nodes.size()), dim3(256), 0, o->stream, o->d_model, o->dt[0], o->d_xs,
                            o->d_us, o->d_xs + n, o->d_shift_nodes, (int)o->shift_nodes.size(), o->T);
+      });
     } else
     hipLaunchKernelGGL((agx::k_shift<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us);
     hipLaunchKernelGGL(agx::k_shift_commit, dim3((int)((n + 255) / 256)), dim3(256), 0, o->stream, o->d_xs, o->d_us, o->B, o->T, o->nx, o->nu);
@@ -2027,7 +2053,9 @@ int agx_ocp_integrate(agx_ocp *o, int n, const double *x, const double *u, doubl
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
     if constexpr (NV > 8)
-      hipLaunchKernelGGL((agx::k_integrate_wg<NV>), dim3(n), dim3(256), 0, o->stream, o->d_model, o->dt[0], dx, du, dn, (const int *)nullptr, 0, 0);
+      launch_wg(o, [&](auto PRc) {
+        hipLaunchKernelGGL((agx::k_integrate_wg<NV, decltype(PRc)::value>), dim3(n), dim3(256), 0, o->stream, o->d_model, o->dt[0], dx, du, dn, (const int *)nullptr, 0, 0);
+      });
     else
       hipLaunchKernelGGL((agx::k_integrate<NV, CH>), dim3((n + 63) / 64), dim3(64), 0, o->stream, o->d_model, o->dt[0], n, dx, du, dn);
     HIPCHK(hipGetLastError());

@@ -183,7 +183,7 @@ struct WgIn {
 
 // Cost rows of one node, evaluated by ONE wave (lane j: component j of the state / control rows, column j of every
 // dense row; lanes >= nv shadow the last joint and store nothing).  Runs next to the wave that solves M qdd = rhs.
-template <int NV, bool TERM, bool DIFF>
+template <int NV, bool TERM, bool DIFF, bool PRISM>
 __device__ __forceinline__ void wg_costs(WgNode<NV> &L, const DevModel &m, const DevRows &rows, const WgIn &in, int lane, double sc) {
   int nJ = 0;
   const int j = lane < NV ? lane : NV - 1;
@@ -243,6 +243,7 @@ __device__ __forceinline__ void wg_costs(WgNode<NV> &L, const DevModel &m, const
       int nr;
       dl[0] = pF[0] - pj[0]; dl[1] = pF[1] - pj[1]; dl[2] = pF[2] - pj[2];
       cross3(Sj + 3, dl, tz);  // z x (pF - pj)
+      prismatic_column(PRISM && ((m.prismatic >> j) & 1u), Sj, tz);
       if (kind == AGX_RES_FRAME_PLACEMENT) {
         nr = 6;
         double Rrel[9], d3[3], prel[3], TL[9], TR[9];
@@ -323,6 +324,8 @@ __device__ __forceinline__ void wg_costs(WgNode<NV> &L, const DevModel &m, const
         for (int e = 0; e < 3; ++e) { da[e] = ca[e] - pj[e]; db[e] = cb[e] - pj[e]; }
         cross3(Sj + 3, da, ta);
         cross3(Sj + 3, db, tb);
+        prismatic_column(PRISM && ((m.prismatic >> j) & 1u), Sj, ta);
+        prismatic_column(PRISM && ((m.prismatic >> j) & 1u), Sj, tb);
         const double g = (ona ? dot3(n, ta) : 0.0) - (onb ? dot3(n, tb) : 0.0);
         Lq += wi * ar * g;
         if (jl) L.w.c.J[nJ][j] = g;
@@ -338,7 +341,9 @@ __device__ __forceinline__ void wg_costs(WgNode<NV> &L, const DevModel &m, const
 }
 
 // DIFF = true: QP tile + aux tile (K1).  DIFF = false: returns cost + mu_dyn |gap|_1 on every thread (line search).
-template <int NV, bool TERM, bool DIFF>
+// PRISM = false: the model has no prismatic joint (the kernels are instantiated both ways and the host picks by the model's
+// mask, so a revolute model runs the instruction stream it ran before joint types existed).
+template <int NV, bool TERM, bool DIFF, bool PRISM>
 __device__ __forceinline__ double wg_node(WgNode<NV> &L, const DevModel &m, const DevRows &rows, const WgIn &in, double *__restrict__ qt,
                                           double *__restrict__ ax) {
   constexpr int NX = 2 * NV, NT = 256, LDM = 32;
@@ -385,24 +390,33 @@ __device__ __forceinline__ double wg_node(WgNode<NV> &L, const DevModel &m, cons
   if (tid < NV) {
     const int i = tid;
     const double *ax3 = m.axis[i];
-    double s, c;
-    sincos(L.x[i], &s, &c);
-    const double omc = 1.0 - c;
-    double Rq[9], Rl[9];
-    Rq[0] = c + omc * ax3[0] * ax3[0];
-    Rq[1] = omc * ax3[0] * ax3[1] - s * ax3[2];
-    Rq[2] = omc * ax3[0] * ax3[2] + s * ax3[1];
-    Rq[3] = omc * ax3[1] * ax3[0] + s * ax3[2];
-    Rq[4] = c + omc * ax3[1] * ax3[1];
-    Rq[5] = omc * ax3[1] * ax3[2] - s * ax3[0];
-    Rq[6] = omc * ax3[2] * ax3[0] - s * ax3[1];
-    Rq[7] = omc * ax3[2] * ax3[1] + s * ax3[0];
-    Rq[8] = c + omc * ax3[2] * ax3[2];
-    mm3(m.placement[i], Rq, Rl);
+    double Rl[9], tq[3] = {0.0, 0.0, 0.0};  // tq: the translation of a prismatic joint, R_fix axis q
+    if (PRISM && ((m.prismatic >> i) & 1u)) {  // prismatic: R_l = R_fix, p_l = p_fix + R_fix axis q
+      mv3(m.placement[i], ax3, tq);
+#pragma unroll
+      for (int e = 0; e < 3; ++e) tq[e] *= L.x[i];
+#pragma unroll
+      for (int e = 0; e < 9; ++e) Rl[e] = m.placement[i][e];
+    } else {
+      double s, c;
+      sincos(L.x[i], &s, &c);
+      const double omc = 1.0 - c;
+      double Rq[9];
+      Rq[0] = c + omc * ax3[0] * ax3[0];
+      Rq[1] = omc * ax3[0] * ax3[1] - s * ax3[2];
+      Rq[2] = omc * ax3[0] * ax3[2] + s * ax3[1];
+      Rq[3] = omc * ax3[1] * ax3[0] + s * ax3[2];
+      Rq[4] = c + omc * ax3[1] * ax3[1];
+      Rq[5] = omc * ax3[1] * ax3[2] - s * ax3[0];
+      Rq[6] = omc * ax3[2] * ax3[0] - s * ax3[1];
+      Rq[7] = omc * ax3[2] * ax3[1] + s * ax3[0];
+      Rq[8] = c + omc * ax3[2] * ax3[2];
+      mm3(m.placement[i], Rq, Rl);
+    }
 #pragma unroll
     for (int e = 0; e < 9; ++e) L.w.c.Rl[i][e] = Rl[e];
 #pragma unroll
-    for (int e = 0; e < 3; ++e) L.w.c.Rl[i][9 + e] = m.placement[i][9 + e];
+    for (int e = 0; e < 3; ++e) L.w.c.Rl[i][9 + e] = PRISM ? m.placement[i][9 + e] + tq[e] : m.placement[i][9 + e];
   }
   __syncthreads();
   AGX_WG_STAMP();
@@ -428,8 +442,13 @@ __device__ __forceinline__ double wg_node(WgNode<NV> &L, const DevModel &m, cons
     const double *R = L.w.c.Rw[i], *p = L.w.c.pw[i];
     double z[3], S[6];
     mv3(R, m.axis[i], z);
-    cross3(p, z, S);
-    S[3] = z[0]; S[4] = z[1]; S[5] = z[2];
+    if (PRISM && ((m.prismatic >> i) & 1u)) {  // prismatic: S = (z ; 0)
+#pragma unroll
+      for (int e = 0; e < 3; ++e) { S[e] = z[e]; S[3 + e] = 0.0; }
+    } else {
+      cross3(p, z, S);
+      S[3] = z[0]; S[4] = z[1]; S[5] = z[2];
+    }
 #pragma unroll
     for (int e = 0; e < 6; ++e) L.S[i][e] = S[e];
     if (!TERM) {
@@ -460,7 +479,7 @@ __device__ __forceinline__ double wg_node(WgNode<NV> &L, const DevModel &m, cons
   if (in.kin_only) return 0.0;  // constraint evaluation (k_con_eval_wg): world placements and joint axes are in LDS
 
   if (TERM) {
-    if (wave == 1) wg_costs<NV, TERM, DIFF>(L, m, rows, in, lane, sc);
+    if (wave == 1) wg_costs<NV, TERM, DIFF, PRISM>(L, m, rows, in, lane, sc);
     __syncthreads();
   } else {
     // ---- bias forces and joint-space inertia; sums along the tree on the matrix cores (tiles (0, 0) and (1, 0): 6 columns)
@@ -542,7 +561,7 @@ __device__ __forceinline__ double wg_node(WgNode<NV> &L, const DevModel &m, cons
         L.fv[lane] = vj + dt * qdd - L.xn[NV + lane];
       }
     } else if (wave == 1) {
-      wg_costs<NV, TERM, DIFF>(L, m, rows, in, lane, sc);
+      wg_costs<NV, TERM, DIFF, PRISM>(L, m, rows, in, lane, sc);
     }
     __syncthreads();
   }
@@ -746,7 +765,7 @@ __device__ __forceinline__ double wg_node(WgNode<NV> &L, const DevModel &m, cons
 // workgroups per CU that latency is covered by the other two; and a persistent variant (768 workgroups walking the units,
 // the next unit's inputs loaded a node ahead) -- 2.7 ms: the loop state pushed the scratch of the 168-register build from
 // 268 to 932 B per lane.
-template <int NV>
+template <int NV, bool PRISM>
 __global__ void __launch_bounds__(256, AGX_WG_MINWAVES) k_calc_qp_wg(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                     const double *__restrict__ dts, const double *__restrict__ xs,
                                                     const double *__restrict__ us, RefView rv, double *__restrict__ qts,
@@ -766,15 +785,15 @@ __global__ void __launch_bounds__(256, AGX_WG_MINWAVES) k_calc_qp_wg(const DevMo
   in.alpha = 0.0; in.preg = k1_preg(st[b], phase); in.mu_dyn = o.mu_dyn;
   in.ref = ref_at(rv, b, t, T); in.stride = o.stride; in.frames = frames_at(rv, b, t, T);
   double *qt = qts + node * QT<NV>::SIZE, *ax = auxs + node * AUX<NV>::SIZE;
-  if (term) { in.dt = 0.0; wg_node<NV, true, true>(L, *mp, o.rows[1], in, qt, ax); }
-  else { in.dt = dts[t]; wg_node<NV, false, true>(L, *mp, o.rows[0], in, qt, ax); }
+  if (term) { in.dt = 0.0; wg_node<NV, true, true, PRISM>(L, *mp, o.rows[1], in, qt, ax); }
+  else { in.dt = dts[t]; wg_node<NV, false, true, PRISM>(L, *mp, o.rows[0], in, qt, ax); }
 }
 
 // Constraint values, Jacobians and the l1 violation of every node for large models (k_con_eval of agx_admm.hpp): control-limit
 // rows (g = u - ref, identity Jacobian on u), state bounds (g = x - ref, identity on x), collision-distance rows (colmpc.ResidualDistanceCollision: g = d(q), Jacobian
 // row on q as in wg_costs) and frame translation / rotation / placement rows (3 / 3 / 6 Jacobian rows on q).  One workgroup per node: the kinematics of wg_node, then wave 0 evaluates the rows, lane j its
 // column.  cg [B][T+1][AGX_MAX_NC], cjac [B][T+1][AGX_MAX_DENSE][32] (d / dq only: no supported row depends on v; u rows are I).
-template <int NV>
+template <int NV, bool PRISM>
 __global__ void __launch_bounds__(256, AGX_WG_MINWAVES) k_con_eval_wg(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                                       const double *__restrict__ xs, const double *__restrict__ us,
                                                                       double *__restrict__ cg, double *__restrict__ cjac,
@@ -797,7 +816,7 @@ __global__ void __launch_bounds__(256, AGX_WG_MINWAVES) k_con_eval_wg(const DevM
     in.u = us + ((long long)b * T + (t < T ? t : T - 1)) * NV; in.du = nullptr; in.alpha = 0.0; in.preg = 0.0; in.mu_dyn = 0.0; in.dt = 0.0;
     in.ref = nullptr; in.stride = 0; in.frames = nullptr; in.kin_only = true;
     __syncthreads();
-    wg_node<NV, true, false>(L, m, none, in, nullptr, nullptr);  // TERM: no successor state / control is read
+    wg_node<NV, true, false, PRISM>(L, m, none, in, nullptr, nullptr);  // TERM: no successor state / control is read
   }
   if (wave != 0) return;
   const int j = lane < NV ? lane : NV - 1;
@@ -832,6 +851,8 @@ __global__ void __launch_bounds__(256, AGX_WG_MINWAVES) k_con_eval_wg(const DevM
       for (int e = 0; e < 3; ++e) { da[e] = ca[e] - pj[e]; db[e] = cb[e] - pj[e]; }
       cross3(Sj + 3, da, ta);
       cross3(Sj + 3, db, tb);
+      prismatic_column(PRISM && ((m.prismatic >> j) & 1u), Sj, ta);
+      prismatic_column(PRISM && ((m.prismatic >> j) & 1u), Sj, tb);
       const double gq = (ona ? dot3(n, ta) : 0.0) - (onb ? dot3(n, tb) : 0.0);
       if (lane < 32) cjac[(node * AGX_MAX_DENSE + c.coll_slot[r]) * 32 + lane] = jl ? gq : 0.0;
       if (lane == 0) {
@@ -869,6 +890,7 @@ __global__ void __launch_bounds__(256, AGX_WG_MINWAVES) k_con_eval_wg(const DevM
 #pragma unroll
       for (int e = 0; e < 3; ++e) d3[e] = pF[e] - pj[e];
       cross3(Sj + 3, d3, tz);  // z x (pF - pj)
+      prismatic_column(PRISM && ((m.prismatic >> j) & 1u), Sj, tz);
       if (kind == AGX_RES_FRAME_TRANSLATION) {
 #pragma unroll
         for (int e = 0; e < 3; ++e) out[e] = tz[e];
@@ -905,7 +927,7 @@ __global__ void __launch_bounds__(256, AGX_WG_MINWAVES) k_con_eval_wg(const DevM
 // workgroup per state, no cost rows.  tlist == null: n packed states x [n][nx], u [n][nu] -> xnext [n][nx].
 // tlist != null (warm-start shift, warm_start_shift_previous_solution.py:98-104: nodes with dt_i > dt_0 are
 // integrated over dt_0): workgroup (b, k) takes node t = tlist[k] of the horizon buffers and writes the staging copy.
-template <int NV>
+template <int NV, bool PRISM>
 __global__ void __launch_bounds__(256) k_integrate_wg(const DevModel *__restrict__ mp, double dt, const double *__restrict__ x,
                                                       const double *__restrict__ u, double *__restrict__ xnext,
                                                       const int *__restrict__ tlist, int nlist, int T) {
@@ -924,7 +946,7 @@ __global__ void __launch_bounds__(256) k_integrate_wg(const DevModel *__restrict
   in.x = x + ix * NX; in.dx = nullptr; in.xn = in.x; in.dxn = nullptr;  // "gap" against x itself: fq = dt v + dt^2 a, fv = dt a
   in.u = u + iu * NV; in.du = nullptr; in.alpha = 0.0; in.preg = 0.0; in.mu_dyn = 0.0; in.dt = dt;
   in.ref = nullptr; in.stride = 0; in.frames = nullptr;
-  wg_node<NV, false, false>(L, *mp, none, in, nullptr, nullptr);
+  wg_node<NV, false, false, PRISM>(L, *mp, none, in, nullptr, nullptr);
   if (threadIdx.x < NV) {
     const int j = threadIdx.x;
     xnext[ix * NX + j] = L.x[j] + L.fq[j];

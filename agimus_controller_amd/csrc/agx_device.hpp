@@ -28,7 +28,9 @@
 #define AGX_MAX_FRAMES 72
 
 struct DevModel {
-  int nv, nframes, is_chain, pad;
+  int nv, nframes, is_chain;
+  unsigned prismatic;  // bit i: joint i translates by q_i along its axis (0: revolute).  A model with one is never a chain
+                       // (is_chain = 0, agx_model_create): the CHAIN instantiations below are revolute only
   int parent[AGX_MAX_NV];
   unsigned anc[AGX_MAX_NV];  // bit j: joint j is i itself or an ancestor of i
   unsigned desc[AGX_MAX_NV]; // bit j: joint j is i itself or a descendant of i (subtree of i)
@@ -246,7 +248,7 @@ template <int NV>
 struct Kin {
   double R[NV][9];  // world rotation of joint frame
   double p[NV][3];  // world position of joint origin
-  double S[NV][6];  // world joint axis (p x z ; z)
+  double S[NV][6];  // world joint axis: revolute (p x z ; z), prismatic (z ; 0)
 };
 
 template <int NV, bool CHAIN>
@@ -257,25 +259,40 @@ AGX_DEV bool is_anc(const DevModel &m, int i, int j) {  // j ancestor-or-self of
 }
 
 template <int NV, bool CHAIN>
+AGX_DEV bool is_prismatic(const DevModel &m, int i) { return !CHAIN && ((m.prismatic >> i) & 1u); }
+// Joint j's column of the Jacobian of a world point P is S_lin + S_ang x P (linear) and S_ang (angular).  The callers form
+// t = z x (P - p_j) with z = S_ang, which is the linear part for a revolute joint; for a prismatic joint, S = (z ; 0), it is
+// S_lin, put in place here.  The angular part needs nothing: S_ang is zero.
+AGX_DEV void prismatic_column(bool pr, const double *S, double *t) {
+  if (pr) { t[0] = S[0]; t[1] = S[1]; t[2] = S[2]; }
+}
+
+template <int NV, bool CHAIN>
 AGX_DEV void kinematics(const DevModel &m, const double *q, Kin<NV> &k) {
 AGX_UNROLL_NV
   for (int i = 0; i < NV; ++i) {
     const double *ax = m.axis[i];
-    double s, c;
-    sincos(q[i], &s, &c);
-    const double omc = 1.0 - c;
-    double Rq[9];
-    Rq[0] = c + omc * ax[0] * ax[0];
-    Rq[1] = omc * ax[0] * ax[1] - s * ax[2];
-    Rq[2] = omc * ax[0] * ax[2] + s * ax[1];
-    Rq[3] = omc * ax[1] * ax[0] + s * ax[2];
-    Rq[4] = c + omc * ax[1] * ax[1];
-    Rq[5] = omc * ax[1] * ax[2] - s * ax[0];
-    Rq[6] = omc * ax[2] * ax[0] - s * ax[1];
-    Rq[7] = omc * ax[2] * ax[1] + s * ax[0];
-    Rq[8] = c + omc * ax[2] * ax[2];
+    const bool pr = is_prismatic<NV, CHAIN>(m, i);
     double Rl[9];
-    mm3(m.placement[i], Rq, Rl);
+    if (pr) {  // prismatic: R_l = R_fix; the translation by q follows below
+#pragma unroll
+      for (int e = 0; e < 9; ++e) Rl[e] = m.placement[i][e];
+    } else {
+      double s, c;
+      sincos(q[i], &s, &c);
+      const double omc = 1.0 - c;
+      double Rq[9];
+      Rq[0] = c + omc * ax[0] * ax[0];
+      Rq[1] = omc * ax[0] * ax[1] - s * ax[2];
+      Rq[2] = omc * ax[0] * ax[2] + s * ax[1];
+      Rq[3] = omc * ax[1] * ax[0] + s * ax[2];
+      Rq[4] = c + omc * ax[1] * ax[1];
+      Rq[5] = omc * ax[1] * ax[2] - s * ax[0];
+      Rq[6] = omc * ax[2] * ax[0] - s * ax[1];
+      Rq[7] = omc * ax[2] * ax[1] + s * ax[0];
+      Rq[8] = c + omc * ax[2] * ax[2];
+      mm3(m.placement[i], Rq, Rl);
+    }
     const int par = parent_of<NV, CHAIN>(m, i);
     if (par >= 0) {
       mm3(k.R[par], Rl, k.R[i]);
@@ -289,8 +306,13 @@ AGX_UNROLL_NV
     }
     double z[3];
     mv3(k.R[i], ax, z);
-    cross3(k.p[i], z, k.S[i]);
-    k.S[i][3] = z[0]; k.S[i][4] = z[1]; k.S[i][5] = z[2];
+    if (pr) {  // the joint frame keeps the orientation R_par R_fix, so z is constant and the origin moves by z q; S = (z ; 0)
+#pragma unroll
+      for (int e = 0; e < 3; ++e) { k.p[i][e] += z[e] * q[i]; k.S[i][e] = z[e]; k.S[i][3 + e] = 0.0; }
+    } else {
+      cross3(k.p[i], z, k.S[i]);
+      k.S[i][3] = z[0]; k.S[i][4] = z[1]; k.S[i][5] = z[2];
+    }
   }
 }
 
@@ -1118,6 +1140,7 @@ AGX_UNROLL_NV
             double lin[3], ang[3], dl[3], t[3];
             dl[0] = pF[0] - k.p[j][0]; dl[1] = pF[1] - k.p[j][1]; dl[2] = pF[2] - k.p[j][2];
             cross3(k.S[j] + 3, dl, t);  // z x (pF - pj)
+            prismatic_column(is_prismatic<NV, CHAIN>(m, j), k.S[j], t);
             mtv3(RF, t, lin);           // LOCAL frame Jacobian column
             mtv3(RF, k.S[j] + 3, ang);
 #pragma unroll
@@ -1141,6 +1164,7 @@ AGX_UNROLL_NV
             double dl[3], t[3];
             dl[0] = pF[0] - k.p[j][0]; dl[1] = pF[1] - k.p[j][1]; dl[2] = pF[2] - k.p[j][2];
             cross3(k.S[j] + 3, dl, t);
+            prismatic_column(is_prismatic<NV, CHAIN>(m, j), k.S[j], t);
 #pragma unroll
             for (int e = 0; e < 3; ++e) { J[e][j] = on ? t[e] : 0.0; J[3 + e][j] = 0.0; }
           }
@@ -1227,6 +1251,8 @@ AGX_UNROLL_NV
           for (int e = 0; e < 3; ++e) { da[e] = ca[e] - k.p[j][e]; db[e] = cb[e] - k.p[j][e]; }
           cross3(k.S[j] + 3, da, ta);
           cross3(k.S[j] + 3, db, tb);
+          prismatic_column(is_prismatic<NV, CHAIN>(m, j), k.S[j], ta);
+          prismatic_column(is_prismatic<NV, CHAIN>(m, j), k.S[j], tb);
           g[j] = (ona ? dot3(n, ta) : 0.0) - (onb ? dot3(n, tb) : 0.0);
         }
 AGX_UNROLL_NV
@@ -1331,6 +1357,7 @@ AGX_UNROLL_NV
 #pragma unroll
           for (int e = 0; e < 3; ++e) d[e] = pF[e] - k.p[j][e];
           cross3(k.S[j] + 3, d, t);  // z x (pF - pj)
+          prismatic_column(is_prismatic<NV, CHAIN>(m, j), k.S[j], t);
           if (kind == AGX_RES_FRAME_TRANSLATION) {
 #pragma unroll
             for (int e = 0; e < 3; ++e) out[e] = t[e];
@@ -1366,6 +1393,8 @@ AGX_UNROLL_NV
           for (int e = 0; e < 3; ++e) { da[e] = ca[e] - k.p[j][e]; db[e] = cb[e] - k.p[j][e]; }
           cross3(k.S[j] + 3, da, ta);
           cross3(k.S[j] + 3, db, tb);
+          prismatic_column(is_prismatic<NV, CHAIN>(m, j), k.S[j], ta);
+          prismatic_column(is_prismatic<NV, CHAIN>(m, j), k.S[j], tb);
           gj[j] = (ona ? dot3(n, ta) : 0.0) - (onb ? dot3(n, tb) : 0.0);
         }
       }

@@ -80,11 +80,12 @@ AGX_DEV void frame_velocity(const DevModel &m, const Kin<NV> &k, int frame, int 
 #pragma unroll
         for (int e = 0; e < 6; ++e) { dq[e] = dW[e]; dv[e] = k.S[kk][e]; }
       } else {
-        // LOCAL_WORLD_ALIGNED: lin = v0_lin + w x pF,  d pF / d q_kk = z x (pF - p_kk)
+        // LOCAL_WORLD_ALIGNED: lin = v0_lin + w x pF,  d pF / d q_kk = z x (pF - p_kk) (prismatic: S_lin; there z = S_ang = 0)
         const double *z = k.S[kk] + 3;
         double d[3], dp[3], t1[3], t2[3], t3[3];
         d[0] = pF[0] - k.p[kk][0]; d[1] = pF[1] - k.p[kk][1]; d[2] = pF[2] - k.p[kk][2];
         cross3(z, d, dp);
+        prismatic_column(is_prismatic<NV, CHAIN>(m, kk), k.S[kk], dp);
         cross3(dW + 3, pF, t1);
         cross3(v0 + 3, dp, t2);
         cross3(z, pF, t3);

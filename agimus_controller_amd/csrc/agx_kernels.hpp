@@ -1598,6 +1598,7 @@ AGX_UNROLL_NV
     double d[3], lin[3], ang[3] = {k.S[j][3], k.S[j][4], k.S[j][5]};
     d[0] = p[0] - k.p[j][0]; d[1] = p[1] - k.p[j][1]; d[2] = p[2] - k.p[j][2];
     cross3(ang, d, lin);
+    prismatic_column(is_prismatic<NV, CHAIN>(m, j), k.S[j], lin);
     if (local) {
       double l2[3], a2[3];
       mtv3(R, lin, l2);

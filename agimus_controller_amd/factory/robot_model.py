@@ -89,7 +89,7 @@ class RobotModelParameters:
 
     def __post_init__(self):
         if self.free_flyer:
-            raise ValueError("free-flyer bases are not supported by the HIP path (1-DoF revolute joints only)")
+            raise ValueError("free-flyer bases are not supported by the HIP path (1-DoF revolute and prismatic joints only)")
         if self.table is None and self.pin_model is None:
             raise ValueError("RobotModelParameters needs a RobotTable (`table`) or a pinocchio model (`pin_model`)")
         if self.table is None:
@@ -144,6 +144,7 @@ class RobotModels:
         return self._q0
 
 
-def panda_robot_models(armature=0.1, q0=None) -> RobotModels:
-    table = robot_tables.panda_table(armature)
-    return RobotModels(RobotModelParameters(table=table, q0=np.zeros(7) if q0 is None else q0, armature=table.armature))
+def panda_robot_models(armature=0.1, q0=None, gripper=False) -> RobotModels:
+    """gripper: the nv = 9 table with the two prismatic finger joints (robot_tables.panda_gripper_table) instead of the 7-joint arm."""
+    table = robot_tables.panda_gripper_table(armature) if gripper else robot_tables.panda_table(armature)
+    return RobotModels(RobotModelParameters(table=table, q0=np.zeros(table.nv) if q0 is None else q0, armature=table.armature))

@@ -3,9 +3,9 @@
 The reference obtains its model from a URDF through Pinocchio
 (agimus_controller/agimus_controller/factory/robot_model.py:88-351).  Neither
 Pinocchio nor any URDF exists in this environment, so the MI355X path takes the
-same information as a plain table: per 1-DoF revolute joint its parent, fixed
-placement, axis, and the spatial inertia of the body it carries; plus named
-operational frames.  `from_pinocchio` converts a `pin.Model` when Pinocchio is
+same information as a plain table: per 1-DoF joint (revolute or prismatic) its
+parent, fixed placement, axis, and the spatial inertia of the body it carries;
+plus named operational frames.  `from_pinocchio` converts a `pin.Model` when Pinocchio is
 importable, so reference users keep their URDF workflow.
 
 The Panda table uses the public Franka kinematics (URDF joint origins) and the
@@ -23,6 +23,10 @@ from __future__ import annotations
 import dataclasses
 
 import numpy as np
+
+
+JOINT_REVOLUTE = 0
+JOINT_PRISMATIC = 1
 
 
 def _rx(a):
@@ -90,6 +94,10 @@ class RobotTable:
     frame_radius: np.ndarray | None = None
     frame_halflen: np.ndarray | None = None
     frame_box: np.ndarray | None = None  # [nframes,3] half extents of box geometry (coal.Box), zeros = not a box
+    joint_type: np.ndarray | None = None
+    """[nv] int, JOINT_REVOLUTE (0) or JOINT_PRISMATIC (1): a prismatic joint translates by q along `axis` (unit, joint frame).
+    None = all revolute.  The CPU checker under oracle/ is revolute only and ignores this field: never hand a table with a
+    prismatic joint to `Oracle` (tests/joint_ref.py is the reference for those)."""
 
     @property
     def nv(self) -> int:
@@ -137,6 +145,12 @@ class RobotTable:
 
 def panda_table(armature=0.1) -> RobotTable:
     """7-DoF Franka Panda, fingers locked and lumped with the hand into link 7."""
+    return _panda_arm(armature, fingers_lumped=True)
+
+
+def _panda_arm(armature, fingers_lumped) -> RobotTable:
+    """The 7-joint arm with the hand lumped into link 7, and the two fingers either lumped in as well (panda_table) or left out
+    (panda_gripper_table carries them as bodies of their own)."""
     hp = np.pi / 2
     origins = [
         (rpy(0, 0, 0), [0, 0, 0.333]),
@@ -174,8 +188,9 @@ def panda_table(armature=0.1) -> RobotTable:
     finger_I = np.diag([2.375e-06, 2.375e-06, 7.5e-07])
     f1 = (0.015, R_hand @ np.array([0.0, 0.0, 0.0584]) + p_hand, finger_I)
     m7, c7, I7 = lump_inertia(mass[6], com[6], inertia[6], *hand)
-    m7, c7, I7 = lump_inertia(m7, c7, I7, *f1)
-    m7, c7, I7 = lump_inertia(m7, c7, I7, *f1)
+    if fingers_lumped:
+        m7, c7, I7 = lump_inertia(m7, c7, I7, *f1)
+        m7, c7, I7 = lump_inertia(m7, c7, I7, *f1)
     mass[6], com[6], inertia[6] = m7, c7, I7
 
     nv = 7
@@ -210,6 +225,38 @@ def panda_table(armature=0.1) -> RobotTable:
         frame_names=frame_names,
         frame_parent=np.array(frame_parent, dtype=np.int32),
         frame_placement=np.stack(frame_placement),
+    )
+
+
+def panda_gripper_table(armature=0.1) -> RobotTable:
+    """9-DoF Franka Panda with its gripper: panda_table with the two fingers taken back out of link 7's lumped inertia (link 7 and
+    the hand stay lumped) and hung on joint 7 as two independent PRISMATIC joints (franka_description: panda_finger_joint1 / 2,
+    origin 0 0 0.0584 in the hand, axes +y / -y of the hand, 0 ... 0.04 m, 0.2 m/s, 20 N).  With both fingers at 0 and at rest the
+    arm dynamics are those of panda_table exactly.  Frames: those of panda_table plus one per fingertip."""
+    t = _panda_arm(0.0, fingers_lumped=False)
+    R_hand = rpy(0, 0, -np.pi / 4)
+    p_finger = np.array([0.0, 0.0, 0.107]) + R_hand @ np.array([0.0, 0.0, 0.0584])
+    fingers = ["panda_finger_joint1", "panda_finger_joint2"]
+    frame_names = list(t.frame_names) + ["panda_leftfinger_tip", "panda_rightfinger_tip"]
+    tip = se3(None, [0.0, 0.0, 0.1034 - 0.0584])  # finger pad: the tcp plane of the hand (0.1034; the finger joints sit at 0.0584)
+    return RobotTable(
+        name="panda_gripper",
+        joint_names=list(t.joint_names) + fingers,
+        parent=np.concatenate([t.parent, [6, 6]]).astype(np.int32),
+        placement=np.vstack([t.placement, se3(R_hand, p_finger)[None, :], se3(R_hand, p_finger)[None, :]]),
+        axis=np.vstack([t.axis, [[0.0, 1.0, 0.0], [0.0, -1.0, 0.0]]]),
+        mass=np.concatenate([t.mass, [0.015, 0.015]]),
+        com=np.vstack([t.com, np.zeros((2, 3))]),
+        inertia=np.vstack([t.inertia, np.tile(np.diag([2.375e-06, 2.375e-06, 7.5e-07]).reshape(1, 9), (2, 1))]),
+        armature=np.broadcast_to(np.asarray(armature, dtype=float), (9,)).copy(),
+        effort_limit=np.concatenate([t.effort_limit, [20.0, 20.0]]),
+        lower_position_limit=np.concatenate([t.lower_position_limit, [0.0, 0.0]]),
+        upper_position_limit=np.concatenate([t.upper_position_limit, [0.04, 0.04]]),
+        velocity_limit=np.concatenate([t.velocity_limit, [0.2, 0.2]]),
+        frame_names=frame_names,
+        frame_parent=np.concatenate([t.frame_parent, [7, 8]]).astype(np.int32),
+        frame_placement=np.vstack([t.frame_placement, tip[None, :], tip[None, :]]),
+        joint_type=np.array([JOINT_REVOLUTE] * 7 + [JOINT_PRISMATIC] * 2, dtype=np.int32),
     )
 
 
@@ -402,16 +449,20 @@ def humanoid30_table(seed: int = 7, armature=0.1) -> RobotTable:
 
 
 def from_pinocchio(model, armature=None) -> RobotTable:  # pragma: no cover - needs pinocchio
-    """Extract a table from a `pinocchio.Model` made of 1-DoF revolute joints."""
+    """Extract a table from a `pinocchio.Model` made of 1-DoF revolute and prismatic joints."""
     nv = model.nv
-    parent, placement, axis, mass, com, inertia = [], [], [], [], [], []
+    parent, placement, axis, mass, com, inertia, joint_type = [], [], [], [], [], [], []
     for j in range(1, model.njoints):
         jm = model.joints[j]
-        assert jm.nv == 1 and jm.nq == 1, "only 1-DoF revolute joints are supported"
         short = jm.shortname()
-        ax = {"JointModelRX": [1.0, 0, 0], "JointModelRY": [0, 1.0, 0], "JointModelRZ": [0, 0, 1.0]}.get(short)
+        assert jm.nv == 1 and jm.nq == 1, (
+            f"joint '{model.names[j]}' ({short}, nq = {jm.nq}, nv = {jm.nv}): only 1-DoF revolute and prismatic joints are supported")
+        ax = {"JointModelRX": [1.0, 0, 0], "JointModelRY": [0, 1.0, 0], "JointModelRZ": [0, 0, 1.0],
+              "JointModelPX": [1.0, 0, 0], "JointModelPY": [0, 1.0, 0], "JointModelPZ": [0, 0, 1.0]}.get(short)
         if ax is None:
             ax = list(np.asarray(jm.extract().axis).reshape(3))
+        joint_type.append(JOINT_PRISMATIC if short in ("JointModelPX", "JointModelPY", "JointModelPZ", "JointModelPrismaticUnaligned")
+                          else JOINT_REVOLUTE)
         parent.append(int(model.parents[j]) - 1)
         M = model.jointPlacements[j]
         placement.append(se3(np.asarray(M.rotation), np.asarray(M.translation)))
@@ -444,4 +495,5 @@ def from_pinocchio(model, armature=None) -> RobotTable:  # pragma: no cover - ne
         frame_parent=np.array(frame_parent, dtype=np.int32),
         frame_placement=np.stack(frame_placement),
         gravity=np.asarray(model.gravity.linear, dtype=float),
+        joint_type=np.array(joint_type, dtype=np.int32),
     )

@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define AGX_MAX_ROWS 8   /* cost rows per node type (running / terminal) that are not collision rows of a wide cost set */
-/* Wide cost sets (serial chains of at most 7 joints after padding): a node type may carry up to AGX_MAX_ROWS rows of any kind
+/* Wide cost sets (serial chains of revolute joints, at most 7 joints after padding): a node type may carry up to AGX_MAX_ROWS rows of any kind
  * followed by up to AGX_MAX_COST_PAIRS AGX_RES_COLLISION rows (soft collision avoidance, one row per collision pair).  The
  * rows stay plain agx_cost_row entries in table order and every collision row owns [item weight | activation weight] at its
  * table offset of the reference tile.  A set is wide when a node type has more than AGX_MAX_ROWS rows (AGX_COST_WIDE=1: any
@@ -41,6 +41,8 @@ extern "C" {
 #define AGX_MAX_COST_PAIRS 64
 #define AGX_MAX_NV 32    /* joints a model table may have; kernels are compiled for nv in {1,2,3,4,6,7} (register-resident
                             path) and 30 (LDS path for large models); other sizes are refused by agx_ocp_create */
+#define AGX_JOINT_REVOLUTE 0   /* agx_model_desc.joint_type */
+#define AGX_JOINT_PRISMATIC 1
 
 /* Residual kinds: class names of the YAML schema,
  * agimus_controller/agimus_controller/ocp/ocp_croco_generic.py:147-550.        */
@@ -110,7 +112,7 @@ typedef struct agx_model_desc {
   int32_t nframes;
   const int32_t *parent;         /* [nv]   parent joint, -1 = world            */
   const double *placement;       /* [nv][12] joint frame in parent joint frame  */
-  const double *axis;            /* [nv][3]  unit revolute axis, joint frame    */
+  const double *axis;            /* [nv][3]  unit axis, joint frame: of rotation (revolute), of translation (prismatic) */
   const double *mass;            /* [nv]                                        */
   const double *com;             /* [nv][3]  joint frame                        */
   const double *inertia;         /* [nv][9]  about com, joint frame             */
@@ -128,6 +130,10 @@ typedef struct agx_model_desc {
    * frame's axes, all 0 = not a box.  Pairs box / capsule and box / sphere are supported, box / box
    * is refused by agx_ocp_create.  NULL = no boxes.                              */
   const double *frame_box;       /* [nframes][3]                                */
+  /* Joint types.  A prismatic joint translates its frame by q along `axis`; its model takes the kernels of a tree of the same size
+   * (the eight-lane kernels, wide cost / constraint sets and the tile carry need a serial chain of revolute joints).  Any other
+   * value is refused by agx_model_create.                                        */
+  const int32_t *joint_type;     /* [nv] 0 = revolute, 1 = prismatic (axis = unit direction of translation, joint frame); NULL = all revolute */
 } agx_model_desc;
 
 /* Shooting problem + solver knobs:
