@@ -240,6 +240,17 @@ def check_cost_rows(rows: T.Sequence[RowSpec], what: str = "node type", wide: bo
                              f"item {seen} ('{rows[seen].name}') has '{r.name}' (item {i}) behind it")
 
 
+def ring_slots(k: int, capacity: int, max_span: int) -> tuple[int, T.Optional[int]]:
+    """Slot arithmetic of a streamed resident trajectory (agx_traj_stream_create, k_traj_append): logical sample k lives in slot
+    k mod capacity of the `capacity + max_span - 1` sample slots of an instance and, when that slot is below max_span - 1, a second
+    time in the mirror slot capacity + (k mod capacity) -- so a window of up to max_span samples starting at logical k0 is contiguous
+    from slot k0 mod capacity.  Returns (slot, mirror slot or None)."""
+    if k < 0 or max_span < 1 or capacity < max_span:
+        raise ValueError(f"ring_slots: need k >= 0 and capacity >= max_span >= 1, got k={k}, capacity={capacity}, max_span={max_span}")
+    slot = k % capacity
+    return slot, (capacity + slot if slot < max_span - 1 else None)
+
+
 def row_offsets(rows: T.Sequence[RowSpec], nv: int) -> list[int]:
     offs, off = [], 0
     for r in rows:

@@ -34,6 +34,8 @@ EXPORTED_SYMBOLS = [
     "agx_ocp_download_async", "agx_ocp_download_wait",
     "agx_traj_generic_create_weighted", "agx_traj_cartesian_sine_wi_create", "agx_traj_get_tile",
     "agx_ocp_set_plant_inertials", "agx_model_sensitivity", "agx_ocp_cost_wide",
+    "agx_traj_stream_create", "agx_traj_stream_append", "agx_traj_stream_release", "agx_traj_stream_range",
+    "agx_traj_stream_joins", "agx_traj_stream_timing",
 ]  # fmt: skip
 
 
@@ -469,6 +471,55 @@ class HipOcp:
                                                      _p(bc(pulsation, (B, 3))), C.c_double(scale_duration), C.c_double(precision), int(it_max),
                                                      _p(bc(w_q, (nv,))), _p(bc(w_qdot, (nv,))), _p(bc(w_effort, (nv,))), _p(bc(w_pose, (6,))),
                                                      int(frame), _p(bc(period, (B, 3))), C.c_double(w_increasing.max_weight), C.c_double(rate)))
+
+    # -- streamed resident trajectory -----------------------------------------
+    def stream_trajectory(self, capacity, max_span, w_q, w_qdot, w_effort, w_pose, frame):
+        """An empty ring of `capacity` samples per instance for windows of up to `max_span` samples (agx_traj_stream_create):
+        stream_append adds samples, stream_release drops the past, and set_window / mpc_step / traj_point / traj_tile take
+        LOGICAL sample indexes (0 = the first sample ever appended)."""
+        nv = self.nv
+        bc = lambda a, shape: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape))  # noqa: E731
+        _chk(lib().agx_traj_stream_create(self._h, int(capacity), int(max_span), _p(bc(w_q, (nv,))), _p(bc(w_qdot, (nv,))),
+                                          _p(bc(w_effort, (nv,))), _p(bc(w_pose, (6,))), int(frame)))
+
+    def stream_append(self, q, dq, ddq, pose=None, w_pose=None, w_collision=None):
+        """Appends m samples per instance: q, dq, ddq [B][m][nv]; pose [B][m][12], w_pose [B][m][6], w_collision [B][m] optional (they
+        broadcast over B), as in generic_trajectory_weighted.  The arrays may be reused at once; the device work runs on the
+        handle's copy stream beside the solver (agx_traj_stream_append states the ordering)."""
+        B, nv = self.B, self.nv
+        q = _f8(q)
+        if q.ndim != 3 or q.shape[0] != B or q.shape[2] != nv:
+            raise ValueError(f"q: expected shape ({B}, m, {nv}), got {q.shape}")
+        m = q.shape[1]
+        dq, ddq = _f8(dq, (B, m, nv)), _f8(ddq, (B, m, nv))
+        bc = lambda a, shape: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape))  # noqa: E731
+        _chk(lib().agx_traj_stream_append(self._h, int(m), _p(q), _p(dq), _p(ddq), _p(bc(pose, (B, m, 12))), _p(bc(w_pose, (B, m, 6))),
+                                          _p(bc(w_collision, (B, m)))))
+
+    def stream_release(self, k: int):
+        """Samples below logical index k are no longer needed (TrajectoryBuffer.clear_past, several at once if wanted)."""
+        _chk(lib().agx_traj_stream_release(self._h, int(k)))
+
+    def stream_range(self):
+        """(first, end): the retained logical samples are [first, end)."""
+        first, end = C.c_int(0), C.c_int(0)
+        _chk(lib().agx_traj_stream_range(self._h, C.byref(first), C.byref(end)))
+        return first.value, end.value
+
+    def stream_joins(self):
+        """(joins, pending): how often the solver stream was made to wait for an append, and the appended pieces not joined yet
+        (debug reader of the ordering contract of agx_traj_stream_append)."""
+        joins, pending = C.c_longlong(0), C.c_int(0)
+        _chk(lib().agx_traj_stream_joins(self._h, C.byref(joins), C.byref(pending)))
+        return joins.value, pending.value
+
+    def stream_timing(self, enable: bool):
+        """Switch the in-situ timing of the two streams on/off; returns (ms_sum[2], count[2]) accumulated so far:
+        [0] the solver stream waiting for fills, [1] transfer + fill of the appended pieces on the copy stream."""
+        ms = (C.c_double * 2)()
+        cnt = (C.c_longlong * 2)()
+        _chk(lib().agx_traj_stream_timing(self._h, 1 if enable else 0, ms, cnt))
+        return list(ms), list(cnt)
 
     def set_horizon_indexes(self, idx):
         """TrajectoryBuffer.horizon_indexes for the resident trajectory (None = uniform)."""

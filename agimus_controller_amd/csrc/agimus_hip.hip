@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -22,6 +23,8 @@ extern "C" int agx_cost_pairs_launch(int dest, void *stream, long long nodes, co
                                      const double *dts, const double *xs, const RefView *rv, double *out, double *auxs, const DevState *st,
                                      int phase, int sel, int which);
 extern "C" int agx_cost_pairs_fill_launch(void *stream, const DevCostWide *w, const double *gw_item, double *traj, long long units, int stride);
+extern "C" int agx_cost_pairs_fill_ring_launch(void *stream, const DevCostWide *w, const double *gw_item, double *traj, int B, int m_new, int end,
+                                               int cap, int mirror, int stride);
 
 namespace {
 
@@ -166,7 +169,33 @@ struct agx_ocp {
   // non-uniform horizon indexes (TrajectoryBuffer): empty = node t looks at sample k0 + t
   std::vector<int> hidx;
   int *d_hidx = nullptr;
-  int win_k0 = 0;
+  int win_logical = -1;  // streamed ring: logical start of the last window set (-1: none since the ring was created)
+  int win_k0 = 0;  // physical start sample of the window (a streamed ring: slot k0 mod capacity)
+  // Streamed resident trajectory (agx_traj_stream_*): d_traj / d_pts hold a ring of st_cap sample slots per
+  // instance followed by st_span - 1 mirror slots (n_points = their sum); logical samples [st_first, st_end) are retained,
+  // sample k in slot k mod st_cap.  An append stages its chunk in one of two page-locked buffers, copies it to the device twin and
+  // fills the slots on the copy stream; ev_st[i] is recorded behind the fill.  st_pending[i]: the solver stream has not been made
+  // to wait for that append yet (done when a window or a reader reaches a sample >= st_lo[i]).
+  bool streamed = false;
+  int st_cap = 0, st_span = 0, st_first = 0, st_end = 0;
+  int st_chunk = 0;  // samples per instance a staging buffer holds (longer appends go in pieces)
+  double *st_host[2] = {nullptr, nullptr}, *d_st_stage[2] = {nullptr, nullptr};
+  hipEvent_t ev_st[2] = {nullptr, nullptr}, ev_st_solver = nullptr;
+  bool st_used[2] = {false, false}, st_pending[2] = {false, false};
+  int st_lo[2] = {0, 0};
+  int st_next = 0;
+  // agx_traj_stream_timing: while on, every join is bracketed by two events on the solver stream ([0]: how long that stream sat
+  // waiting for a fill) and every appended piece by two on the copy stream ([1]: transfer + fill); pairs are kept until read
+  bool st_timing = false;
+  std::vector<hipEvent_t> st_tev[2];  // [kind][2 * k] start, [2 * k + 1] stop
+  size_t st_tev_used[2] = {0, 0};
+  double st_tms[2] = {0.0, 0.0};
+  long long st_tn[2] = {0, 0};
+  long long st_joins = 0;  // times the solver stream was made to wait for an append (agx_traj_stream_joins)
+  agx::SineParams st_sp{};  // weights and frame given at create
+  // the device work of the last appended piece (agx_ocp_time_kernel(10) repeats it): staging buffer, samples, logical start,
+  // doubles copied, kernel parameters
+  struct { int buf = -1, m = 0, end = 0; size_t used = 0; agx::SineParams sp{}; } st_last;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_done = nullptr;
   int last_max_iter = 0;
   // in-situ kernel timing (agx_ocp_profile): event pairs around the launches of the SQP loop
@@ -1033,6 +1062,63 @@ int ensure_copy_stream(agx_ocp *o) {
   return 0;
 }
 
+// The handle stops being a streamed ring (another trajectory is created, or a new ring): fills still queued on the copy stream
+// write d_traj / d_pts, so the host waits for them before those are freed.  The staging buffers go too: a new ring sizes its own.
+int stream_end(agx_ocp *o) {
+  if (!o->streamed) return 0;
+  HIPCHK(hipStreamSynchronize(o->copy_stream));
+  for (int i = 0; i < 2; ++i) {
+    if (o->d_st_stage[i]) { (void)hipFree(o->d_st_stage[i]); o->d_st_stage[i] = nullptr; }
+    if (o->st_host[i]) { (void)hipHostFree(o->st_host[i]); o->st_host[i] = nullptr; }
+    o->st_used[i] = o->st_pending[i] = false;
+  }
+  o->streamed = false;
+  o->st_last.buf = -1;
+  o->st_cap = o->st_span = o->st_first = o->st_end = o->st_chunk = 0;
+  return 0;
+}
+int stream_enqueue_last(agx_ocp *o, bool behind_solver);
+// next event of the timing pairs of `kind`, recorded on `s` (events are created once and reused after every read-out)
+int stream_time_mark(agx_ocp *o, int kind, hipStream_t s) {
+  if (!o->st_timing) return 0;
+  if (o->st_tev_used[kind] == o->st_tev[kind].size()) {
+    hipEvent_t e = nullptr;
+    HIPCHK(hipEventCreate(&e));
+    o->st_tev[kind].push_back(e);
+  }
+  HIPCHK(hipEventRecord(o->st_tev[kind][o->st_tev_used[kind]++], s));
+  return 0;
+}
+// The solver stream waits (the host does not) for every append not yet joined that wrote a sample below `upto`.
+int stream_join(agx_ocp *o, int upto) {
+  for (int n = 0; n < 2; ++n) {
+    const int i = (o->st_next + n) % 2;  // the older buffer first
+    if (o->st_pending[i] && o->st_lo[i] < upto) {
+      if (stream_time_mark(o, 0, o->stream)) return -1;
+      HIPCHK(hipStreamWaitEvent(o->stream, o->ev_st[i], 0));
+      if (stream_time_mark(o, 0, o->stream)) return -1;
+      o->st_pending[i] = false;
+      ++o->st_joins;
+    }
+  }
+  return 0;
+}
+// Sample index of a resident trajectory as the kernels and copies address it: `k` itself, or on a streamed ring the slot of
+// logical sample k, with the samples [k, k + span) required inside [first, end) and their appends joined.
+int traj_locate(agx_ocp *o, const char *fn, const char *what, int k, int span, int *phys) {
+  if (!o->streamed) {
+    if (k < 0 || (long long)k + span > o->n_points) return fail(std::string(fn) + ": " + what);
+    *phys = k;
+    return 0;
+  }
+  if (k < o->st_first || (long long)k + span > o->st_end)
+    return fail(std::string(fn) + ": samples [" + std::to_string(k) + ", " + std::to_string((long long)k + span) + ") are not inside the retained range [first, end) = [" +
+                std::to_string(o->st_first) + ", " + std::to_string(o->st_end) + ") of the streamed trajectory");
+  if (stream_join(o, k + span)) return -1;
+  *phys = k % o->st_cap;
+  return 0;
+}
+
 // Trial rounds of the line search of SQP iteration `it` (nv <= 7; k_sqp_head has written the first trial iterate):
 // derivative pass (+ constraint evaluation) at the trial points, k_sqp_accept, and -- only while the counter of handed-on
 // trials grows, i.e. when somebody rejected a step length -- the same again.  The finished-instance count comes back
@@ -1671,6 +1757,13 @@ void agx_ocp_destroy(agx_ocp *o) {
   if (o->ev_refs) (void)hipEventDestroy(o->ev_refs);
   if (o->ev_snap) (void)hipEventDestroy(o->ev_snap);
   if (o->ev_dl) (void)hipEventDestroy(o->ev_dl);
+  for (int i = 0; i < 2; ++i) {
+    if (o->d_st_stage[i]) (void)hipFree(o->d_st_stage[i]);
+    if (o->st_host[i]) (void)hipHostFree(o->st_host[i]);
+    if (o->ev_st[i]) (void)hipEventDestroy(o->ev_st[i]);
+    for (hipEvent_t e : o->st_tev[i]) (void)hipEventDestroy(e);
+  }
+  if (o->ev_st_solver) (void)hipEventDestroy(o->ev_st_solver);
   if (o->copy_stream) (void)hipStreamDestroy(o->copy_stream);
   if (o->d_first && !o->poll) (void)hipFree(o->d_first);
   if (o->h_first) (void)hipHostFree(o->h_first);
@@ -2255,6 +2348,22 @@ int agx_dev_wg_stamps(long long *out, int *n) {
 int agx_ocp_time_kernel(agx_ocp *o, int which, int reps, double *avg_ms) {
   if (!o || !avg_ms || reps < 1) return fail("agx_ocp_time_kernel: bad argument");
   if (set_device(o)) return -1;
+  if (which == 10) {  // the device work of the last stream append again (same chunk, same slots, same values), on the copy stream
+    if (!o->streamed || o->st_last.buf < 0) return fail("agx_ocp_time_kernel: which = 10 needs a streamed trajectory with an append");
+    HIPCHK(hipStreamSynchronize(o->stream));
+    HIPCHK(hipStreamSynchronize(o->copy_stream));
+    for (int pass = 0; pass < 2; ++pass) {
+      if (pass == 1) HIPCHK(hipEventRecord(o->ev0, o->copy_stream));
+      for (int r = 0; r < (pass == 0 ? 1 : reps); ++r)
+        if (stream_enqueue_last(o, false)) return -1;
+    }
+    HIPCHK(hipEventRecord(o->ev1, o->copy_stream));
+    HIPCHK(hipEventSynchronize(o->ev1));
+    float ms10 = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms10, o->ev0, o->ev1));
+    *avg_ms = (double)ms10 / reps;
+    return 0;
+  }
   // state for the timed kernel: fresh solver state, QP tiles and a direction at the resident point
   if (carry_invalidate(o)) return -1;
   if (reset_state(o)) return -1;
@@ -2345,6 +2454,7 @@ int agx_traj_sine_create(agx_ocp *o, int n_points, double dt, const double *q0, 
   if (frame < 0 || frame >= o->hm.nframes) return fail("agx_traj_sine_create: frame id out of range");
   if (set_device(o)) return -1;
   if (carry_invalidate(o)) return -1;
+  if (stream_end(o)) return -1;
   const size_t B = o->B, nv = o->nv;
   if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
   if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
@@ -2392,6 +2502,7 @@ static int traj_generic_build(agx_ocp *o, const char *fn, int n_points, const do
   if (frame < 0 || frame >= o->hm.nframes) return fail(name + ": frame id out of range");
   if (set_device(o)) return -1;
   if (carry_invalidate(o)) return -1;
+  if (stream_end(o)) return -1;
   const size_t B = o->B, nv = o->nv, np = B * (size_t)n_points, n = np * nv;
   if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
   if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
@@ -2472,6 +2583,7 @@ static int traj_cartesian_build(agx_ocp *o, const char *fn, int n_points, double
   }
   if (set_device(o)) return -1;
   if (carry_invalidate(o)) return -1;
+  if (stream_end(o)) return -1;
   const size_t B = o->B, nv = o->nv, n = B * (size_t)n_points * nv;
   if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
   if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
@@ -2564,6 +2676,9 @@ int agx_traj_cartesian_sine_wi_create(agx_ocp *o, int n_points, double dt, const
 int agx_traj_set_horizon_indexes(agx_ocp *o, const int32_t *idx) {
   if (!o) return fail("null handle");
   if (set_device(o)) return -1;
+  if (o->streamed && idx && idx[o->T] >= 0 && idx[o->T] + 1 > o->st_span)
+    return fail("agx_traj_set_horizon_indexes: the window covers idx[T] + 1 = " + std::to_string(idx[o->T] + 1) + " samples, the streamed trajectory was created with max_span " +
+                std::to_string(o->st_span));
   if (carry_invalidate(o)) return -1;
   o->hidx.clear();
   if (!idx) return 0;  // back to uniform
@@ -2584,7 +2699,10 @@ int agx_traj_set_window(agx_ocp *o, int k0) {
   if (!o) return fail("null handle");
   if (!o->d_traj) return fail("agx_traj_set_window: no resident trajectory");
   const int last = o->hidx.empty() ? o->T : o->hidx[o->T];
-  if (k0 < 0 || k0 + last + 1 > o->n_points) return fail("agx_traj_set_window: window leaves the trajectory");
+  if (o->streamed && set_device(o)) return -1;
+  const int k0_logical = k0;
+  if (traj_locate(o, "agx_traj_set_window", "window leaves the trajectory", k0_logical, last + 1, &k0)) return -1;
+  o->win_logical = k0_logical;
   o->win_k0 = k0;
   o->rv.frames = o->d_frames;
   if (o->hidx.empty()) {
@@ -2608,8 +2726,8 @@ int agx_traj_set_window(agx_ocp *o, int k0) {
 
 int agx_traj_get_point(agx_ocp *o, int k, double *q, double *v, double *a, double *u, double *pose) {
   if (!o || !o->d_pts) return fail("agx_traj_get_point: no resident trajectory");
-  if (k < 0 || k >= o->n_points) return fail("agx_traj_get_point: sample out of range");
   if (set_device(o)) return -1;
+  if (traj_locate(o, "agx_traj_get_point", "sample out of range", k, 1, &k)) return -1;
   const size_t B = o->B, nv = o->nv, w = 4 * nv + 12;
   std::vector<double> h(B * w);
   HIPCHK(hipMemcpy2DAsync(h.data(), sizeof(double) * w, o->d_pts + (size_t)k * w, sizeof(double) * o->n_points * w, sizeof(double) * w, B, hipMemcpyDeviceToHost, o->stream));
@@ -2629,8 +2747,8 @@ int agx_traj_get_point(agx_ocp *o, int k, double *q, double *v, double *a, doubl
 int agx_traj_get_tile(agx_ocp *o, int k, int terminal, double *out) {
   if (!o || !out) return fail("agx_traj_get_tile: null argument");
   if (!o->d_traj) return fail("agx_traj_get_tile: no resident trajectory");
-  if (k < 0 || k >= o->n_points) return fail("agx_traj_get_tile: sample out of range");
   if (set_device(o)) return -1;
+  if (traj_locate(o, "agx_traj_get_tile", "sample out of range", k, 1, &k)) return -1;
   if (carry_invalidate(o)) return -1;
   const size_t B = o->B, st = o->stride, su = o->stride_u;
   const int lay = terminal ? 1 : 0;
@@ -2661,6 +2779,11 @@ static int ws_from_ref(agx_ocp *o, int k0, int set_x0) {
 int agx_traj_warmstart_from_reference(agx_ocp *o) {
   if (!o || !o->d_pts) return fail("agx_traj_warmstart_from_reference: no resident trajectory");
   if (set_device(o)) return -1;
+  if (o->streamed) {  // the window may have been released, or never set
+    int phys = 0;
+    if (o->win_logical < 0) return fail("agx_traj_warmstart_from_reference: no window set on the streamed trajectory");
+    if (traj_locate(o, "agx_traj_warmstart_from_reference", "", o->win_logical, (o->hidx.empty() ? o->T : o->hidx[o->T]) + 1, &phys)) return -1;
+  }
   if (carry_invalidate(o)) return -1;
   return ws_from_ref(o, o->win_k0, 1);
 }
@@ -2770,7 +2893,7 @@ int agx_ocp_mpc_step(agx_ocp *o, int k0, int max_iter, int first) {
   if (!carry && carry_invalidate(o)) return -1;
   o->carry_armed = false;  // until this step has gone through
   if (first == 1) {
-    if (ws_from_ref(o, k0, 1)) return -1;
+    if (ws_from_ref(o, o->win_k0, 1)) return -1;  // (the physical window start: k0 itself unless the trajectory is a streamed ring)
   } else {
     // x0 <- xs[1] (first == 0; first == 2: x0 was set by the caller / the feedback rollout), warm-start
     // shift, x0 pin and state reset: one launch when the shifted nodes of an instance fit in LDS
@@ -2797,6 +2920,207 @@ int agx_ocp_mpc_step(agx_ocp *o, int k0, int max_iter, int first) {
   if (solve_resident(o, max_iter, 0.0, prologue_done, carry_mode)) return -1;
   o->carry_armed = o->carry_static;
   o->carry_k0 = k0;
+  return 0;
+}
+
+// ---- streamed resident trajectory ---------------------------------------------------------------------------------------------
+// doubles one (instance, sample) of a staged chunk takes: q | dq | ddq at the capacity nv, pose 12, pose weights 6, collision weight 1
+static size_t stream_sample_doubles(const agx_ocp *o) { return 3 * (size_t)o->nv + 19; }
+
+int agx_traj_stream_create(agx_ocp *o, int capacity, int max_span, const double *w_q, const double *w_qdot, const double *w_effort,
+                           const double *w_pose, int frame) {
+  if (!o || !w_q || !w_qdot || !w_effort || !w_pose) return fail("agx_traj_stream_create: null argument");
+  if (max_span < o->T + 1) return fail("agx_traj_stream_create: max_span " + std::to_string(max_span) + " is below the T + 1 = " + std::to_string(o->T + 1) + " samples of a window");
+  if (capacity < max_span) return fail("agx_traj_stream_create: capacity " + std::to_string(capacity) + " is below max_span " + std::to_string(max_span));
+  if (frame < 0 || frame >= o->hm.nframes) return fail("agx_traj_stream_create: frame id out of range");
+  if ((long long)capacity + max_span - 1 > INT_MAX) return fail("agx_traj_stream_create: capacity + max_span - 1 does not fit an int");
+  // horizon indexes set earlier stay with the handle: their window must fit the mirror too (agx_traj_set_horizon_indexes checks later ones)
+  if (!o->hidx.empty() && o->hidx[o->T] + 1 > max_span)
+    return fail("agx_traj_stream_create: the horizon indexes of the handle cover idx[T] + 1 = " + std::to_string(o->hidx[o->T] + 1) +
+                " samples, max_span is " + std::to_string(max_span));
+  if (set_device(o)) return -1;
+  if (carry_invalidate(o)) return -1;
+  if (stream_end(o)) return -1;
+  if (ensure_copy_stream(o)) return -1;
+  const size_t B = o->B, nv = o->nv;
+  if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
+  if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
+  if (o->d_sine) { (void)hipFree(o->d_sine); o->d_sine = nullptr; }
+  o->n_points = 0;
+  // no window yet: the solver looks at the handle's own tile until agx_traj_set_window / agx_ocp_mpc_step finds one in the ring
+  o->rv.base = o->d_ref;
+  o->rv.bstride = (long long)(o->T + 1) * o->stride;
+  o->rv.tstride = o->stride;
+  o->rv.term_off = 0;
+  o->rv.frames = nullptr;
+  const size_t n_slots = (size_t)capacity + max_span - 1;
+  HIPCHK(hipMalloc((void **)&o->d_traj, sizeof(double) * B * n_slots * 2 * o->stride));
+  HIPCHK(hipMalloc((void **)&o->d_pts, sizeof(double) * B * n_slots * (4 * nv + 12)));
+  HIPCHK(hipMemsetAsync(o->d_traj, 0, sizeof(double) * B * n_slots * 2 * o->stride, o->stream));
+  HIPCHK(hipMemsetAsync(o->d_pts, 0, sizeof(double) * B * n_slots * (4 * nv + 12), o->stream));
+  o->st_chunk = max_span;
+  const size_t stage = sizeof(double) * B * (size_t)o->st_chunk * stream_sample_doubles(o);
+  for (int i = 0; i < 2; ++i) {
+    HIPCHK(hipHostMalloc((void **)&o->st_host[i], stage, hipHostMallocDefault));
+    HIPCHK(hipMalloc((void **)&o->d_st_stage[i], stage));
+    if (!o->ev_st[i]) HIPCHK(hipEventCreateWithFlags(&o->ev_st[i], hipEventDisableTiming));
+  }
+  if (!o->ev_st_solver) HIPCHK(hipEventCreateWithFlags(&o->ev_st_solver, hipEventDisableTiming));
+  agx::SineParams &sp = o->st_sp;
+  std::memset(&sp, 0, sizeof(sp));
+  for (size_t i = 0; i < nv; ++i) {  // pad joints: weight 1 on an identically zero residual
+    const bool real = i < (size_t)o->nvu;
+    sp.w_q[i] = real ? w_q[i] : 1.0; sp.w_qdot[i] = real ? w_qdot[i] : 1.0; sp.w_effort[i] = real ? w_effort[i] : 1.0;
+  }
+  for (int i = 0; i < 6; ++i) sp.w_pose[i] = w_pose[i];
+  sp.dt = 0.0; sp.n_points = (int)n_slots; sp.frame = frame;
+  o->n_points = (int)n_slots;
+  o->st_cap = capacity; o->st_span = max_span; o->st_first = o->st_end = 0; o->st_next = 0;
+  o->win_logical = -1;
+  o->streamed = true;
+  return traj_frames(o, frame);  // (waits for the solver stream: the ring is zeroed when this returns)
+}
+
+}  // extern "C"
+namespace {
+// Transfer of the staged piece o->st_last and fill of its slots, on the copy stream.  behind_solver: the fill waits for what the
+// solver stream holds at this moment, which may still read the slots released since (the transfer need not wait: the device
+// half of a staging buffer is read by fills of the copy stream only).
+int stream_enqueue_last(agx_ocp *o, bool behind_solver) {
+  const auto &L = o->st_last;
+  if (behind_solver && stream_time_mark(o, 1, o->copy_stream)) return -1;
+  HIPCHK(hipMemcpyAsync(o->d_st_stage[L.buf], o->st_host[L.buf], sizeof(double) * L.used, hipMemcpyHostToDevice, o->copy_stream));
+  if (behind_solver) {
+    HIPCHK(hipEventRecord(o->ev_st_solver, o->stream));
+    HIPCHK(hipStreamWaitEvent(o->copy_stream, o->ev_st_solver, 0));
+  }
+  const long long units = (long long)o->B * L.m;
+  int rc = dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
+    constexpr int NV = decltype(NVc)::value;
+    constexpr bool CH = decltype(CHc)::value;
+    hipLaunchKernelGGL((agx::k_traj_append<NV, CH>), dim3((unsigned)((units + 63) / 64)), dim3(64), 0, o->copy_stream, o->d_model, o->d_ocp, L.sp, o->d_traj,
+                       o->d_pts, L.m, L.end, o->st_cap, o->st_span - 1);
+    HIPCHK(hipGetLastError());
+    return 0;
+  });
+  if (rc) return rc;
+  if (o->cost_wide)
+    HIPCHK((hipError_t)agx_cost_pairs_fill_ring_launch((void *)o->copy_stream, o->d_cw, L.sp.gw_item, o->d_traj, o->B, L.m, L.end, o->st_cap, o->st_span - 1,
+                                                       o->stride));
+  if (behind_solver && stream_time_mark(o, 1, o->copy_stream)) return -1;
+  return 0;
+}
+}  // namespace
+extern "C" {
+
+int agx_traj_stream_timing(agx_ocp *o, int enable, double *ms_sum, long long *count) {
+  if (!o) return fail("null handle");
+  if (set_device(o)) return -1;
+  // read out what has been recorded: both streams have to be through with it
+  if (o->st_tev_used[0] || o->st_tev_used[1]) {
+    HIPCHK(hipStreamSynchronize(o->stream));
+    if (o->copy_stream) HIPCHK(hipStreamSynchronize(o->copy_stream));
+    for (int kind = 0; kind < 2; ++kind) {
+      for (size_t k = 0; k + 1 < o->st_tev_used[kind]; k += 2) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, o->st_tev[kind][k], o->st_tev[kind][k + 1]));
+        o->st_tms[kind] += ms;
+        o->st_tn[kind] += 1;
+      }
+      o->st_tev_used[kind] = 0;
+    }
+  }
+  if (ms_sum && count)
+    for (int kind = 0; kind < 2; ++kind) { ms_sum[kind] = o->st_tms[kind]; count[kind] = o->st_tn[kind]; }
+  if ((enable != 0) != o->st_timing) {
+    o->st_timing = enable != 0;
+    for (int kind = 0; kind < 2; ++kind) { o->st_tms[kind] = 0.0; o->st_tn[kind] = 0; }
+  }
+  return 0;
+}
+
+int agx_traj_stream_append(agx_ocp *o, int m, const double *q, const double *dq, const double *ddq, const double *pose, const double *w_pose,
+                           const double *w_collision) {
+  if (!o || !q || !dq || !ddq) return fail("agx_traj_stream_append: null argument");
+  if (!o->streamed) return fail("agx_traj_stream_append: the handle has no streamed trajectory (agx_traj_stream_create)");
+  if (m < 1) return fail("agx_traj_stream_append: m must be at least 1");
+  if (m > INT_MAX - o->st_end) return fail("agx_traj_stream_append: end + m does not fit an int (logical sample indexes are int)");
+  if ((long long)o->st_end + m - o->st_first > o->st_cap)
+    return fail("agx_traj_stream_append: " + std::to_string(m) + " more samples overflow the ring, release the past first (first " + std::to_string(o->st_first) +
+                ", end " + std::to_string(o->st_end) + ", capacity " + std::to_string(o->st_cap) + ")");
+  const size_t B = o->B, nv = o->nv, nvu = o->nvu, np = B * (size_t)m;
+  struct { const double *a; size_t n; const char *name; } in[] = {{q, np * nvu, "q"}, {dq, np * nvu, "dq"}, {ddq, np * nvu, "ddq"}, {pose, np * 12, "pose"},
+                                                               {w_pose, np * 6, "w_pose"}, {w_collision, np, "w_collision"}};
+  for (const auto &c : in)
+    if (c.a)
+      for (size_t i = 0; i < c.n; ++i)
+        if (!std::isfinite(c.a[i])) return fail(std::string("agx_traj_stream_append: non-finite value in ") + c.name + " (element " + std::to_string(i) + ")");
+  if (set_device(o)) return -1;
+  // pieces of at most st_chunk samples, one staging buffer each
+  for (int j0 = 0; j0 < m; j0 += o->st_chunk) {
+    const int mp = std::min(o->st_chunk, m - j0);
+    const int i = o->st_next;
+    // the buffer's previous piece: its copy and its fill have to be over before the host rewrites the page-locked half and the
+    // copy stream the device half.  The fill is then complete for everybody: nothing is left to join.
+    if (o->st_used[i]) {
+      HIPCHK(hipEventSynchronize(o->ev_st[i]));
+      o->st_pending[i] = false;
+    }
+    const size_t npp = B * (size_t)mp, n = npp * nv;
+    double *h = o->st_host[i], *d = o->d_st_stage[i];
+    const double *src3[3] = {q, dq, ddq};
+    const bool whole = mp == m;  // one piece: the caller's [B][m] arrays have the layout of the chunk
+    for (int a = 0; a < 3; ++a) {
+      if (whole && !o->padded) { std::memcpy(h + a * n, src3[a], sizeof(double) * n); continue; }
+      for (size_t b = 0; b < B; ++b)
+        pad_rows(h + a * n + b * mp * nv, src3[a] + (b * m + j0) * nvu, (size_t)mp, 1, (int)nvu, (int)nv, 0.0);
+    }
+    size_t used = 3 * n;
+    agx::SineParams sp = o->st_sp;
+    sp.gq = d; sp.gdq = d + n; sp.gddq = d + 2 * n;
+    struct { const double *a; size_t w; const double **dst; } opt[] = {{pose, 12, &sp.gpose}, {w_pose, 6, &sp.gw_pose}, {w_collision, 1, &sp.gw_item}};
+    for (const auto &c : opt)
+      if (c.a) {
+        if (whole) std::memcpy(h + used, c.a, sizeof(double) * npp * c.w);
+        else
+          for (size_t b = 0; b < B; ++b) std::memcpy(h + used + b * mp * c.w, c.a + (b * m + j0) * c.w, sizeof(double) * mp * c.w);
+        *c.dst = d + used;
+        used += npp * c.w;
+      }
+    const int end = o->st_end;
+    o->st_last.buf = i; o->st_last.m = mp; o->st_last.end = end; o->st_last.used = used; o->st_last.sp = sp;
+    if (stream_enqueue_last(o, true)) return -1;
+    HIPCHK(hipEventRecord(o->ev_st[i], o->copy_stream));
+    o->st_used[i] = o->st_pending[i] = true;
+    o->st_lo[i] = end;
+    o->st_end = end + mp;
+    o->st_next = 1 - i;
+  }
+  return 0;
+}
+
+int agx_traj_stream_release(agx_ocp *o, int k) {
+  if (!o) return fail("null handle");
+  if (!o->streamed) return fail("agx_traj_stream_release: the handle has no streamed trajectory (agx_traj_stream_create)");
+  if (k < o->st_first || k > o->st_end)
+    return fail("agx_traj_stream_release: " + std::to_string(k) + " is outside [first, end] = [" + std::to_string(o->st_first) + ", " + std::to_string(o->st_end) + "]");
+  o->st_first = k;
+  return 0;
+}
+
+int agx_traj_stream_joins(agx_ocp *o, long long *joins, int *pending) {
+  if (!o) return fail("null handle");
+  if (!o->streamed) return fail("agx_traj_stream_joins: the handle has no streamed trajectory (agx_traj_stream_create)");
+  if (joins) *joins = o->st_joins;
+  if (pending) *pending = (o->st_pending[0] ? 1 : 0) + (o->st_pending[1] ? 1 : 0);
+  return 0;
+}
+
+int agx_traj_stream_range(agx_ocp *o, int *first, int *end) {
+  if (!o) return fail("null handle");
+  if (!o->streamed) return fail("agx_traj_stream_range: the handle has no streamed trajectory (agx_traj_stream_create)");
+  if (first) *first = o->st_first;
+  if (end) *end = o->st_end;
   return 0;
 }
 

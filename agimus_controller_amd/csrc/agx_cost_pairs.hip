@@ -25,4 +25,13 @@ int agx_cost_pairs_fill_launch(void *stream, const DevCostWide *w, const double 
   return (int)hipGetLastError();
 }
 
+// k_cost_pairs_fill_ring for the chunk a stream append adds (see the kernel)
+int agx_cost_pairs_fill_ring_launch(void *stream, const DevCostWide *w, const double *gw_item, double *traj, int B, int m_new, int end, int cap,
+                                    int mirror, int stride) {
+  const long long n = (long long)B * m_new * 2;
+  hipLaunchKernelGGL(agx::k_cost_pairs_fill_ring, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, gw_item, traj, B, m_new,
+                     end, cap, mirror, stride);
+  return (int)hipGetLastError();
+}
+
 }  // extern "C"

@@ -228,4 +228,28 @@ __global__ void k_cost_pairs_fill(const DevCostWide *__restrict__ wp, const doub
   }
 }
 
+// The same for the samples agx_traj_stream_append adds to a streamed ring (k_traj_append: `cap` slots + `mirror` mirror slots per
+// instance, n_points = cap + mirror): sample j of the chunk [B][m_new] goes to slot (end + j) mod cap and to its mirror slot;
+// gw_item [B][m_new] (optional) is the chunk's scheduled item weight.
+__global__ void k_cost_pairs_fill_ring(const DevCostWide *__restrict__ wp, const double *__restrict__ gw_item, double *__restrict__ traj,
+                                       int B, int m_new, int end, int cap, int mirror, int stride) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)B * m_new * 2) return;
+  const long long unit = i >> 1;
+  const int layout = (int)(i & 1);
+  const int b = (int)(unit / m_new), j = (int)(unit % m_new);
+  const int slot = (int)(((long long)end + j) % cap);
+  const DevCostPairs &P = wp->lay[layout];
+  const double w = gw_item ? gw_item[unit] : 0.0;
+  for (int copy = 0; copy < 2; ++copy) {
+    if (copy && slot >= mirror) break;
+    const long long dst = (long long)b * (cap + mirror) + slot + (copy ? cap : 0);
+    double *tile = traj + dst * 2 * stride + (long long)layout * stride + P.prefix;
+    for (int p = 0; p < P.n; ++p) {
+      tile[2 * p] = gw_item ? w : P.weight[p];
+      tile[2 * p + 1] = 1.0;
+    }
+  }
+}
+
 }  // namespace agx

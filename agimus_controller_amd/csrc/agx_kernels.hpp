@@ -1893,6 +1893,70 @@ struct SineParams {
   int n_points, frame;
 };
 
+// One sample of a resident trajectory from its q, dq, ddq: feed-forward effort by RNEA, pose of sp.frame (or the caller's pose),
+// then the raw point and both reference tiles.  `src` indexes the caller-given per-sample arrays of sp (gpose, gw_pose, gw_item),
+// `dst` the sample slot of traj / pts it is written to and `dst2` a second slot that receives the same values (< 0: none; the
+// mirror slot of a streamed ring).  Shared by k_sine_fill and k_traj_append: the two differ in src / dst only.
+template <int NV, bool CHAIN>
+__device__ __forceinline__ void traj_sample_write(const DevModel &m, const DevOcp &o, const SineParams &sp, long long src, const double *q,
+                                                  const double *dq, const double *ddq, double *__restrict__ traj, double *__restrict__ pts,
+                                                  long long dst, long long dst2) {
+  double u[NV];
+  Kin<NV> k;
+  kinematics<NV, CHAIN>(m, q, k);
+  rnea<NV, CHAIN>(m, k, dq, ddq, u);
+  double RF[9], pF[3];
+  int jf;
+  frame_world<NV>(m, k, sp.frame, RF, pF, &jf);
+  if (sp.gpose) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) RF[e] = sp.gpose[src * 12 + e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) pF[e] = sp.gpose[src * 12 + 9 + e];
+  }
+  double wp[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) wp[e] = sp.gw_pose ? sp.gw_pose[src * 6 + e] : sp.w_pose[e];
+  for (int copy = 0; copy < 2; ++copy) {
+    const long long unit = copy ? dst2 : dst;
+    if (unit < 0) break;
+    double *pt = pts + unit * (4 * NV + 12);
+AGX_UNROLL_NV
+    for (int i = 0; i < NV; ++i) { pt[i] = q[i]; pt[NV + i] = dq[i]; pt[2 * NV + i] = ddq[i]; pt[3 * NV + i] = u[i]; }
+AGX_UNROLL_NV
+    for (int e = 0; e < 9; ++e) pt[4 * NV + e] = RF[e];
+AGX_UNROLL_NV
+    for (int e = 0; e < 3; ++e) pt[4 * NV + 9 + e] = pF[e];
+    for (int layout = 0; layout < 2; ++layout) {
+      const DevRows &rows = o.rows[layout];
+      double *tile = traj + unit * 2 * o.stride + layout * o.stride;
+      for (int r = 0; r < rows.n; ++r) {
+        double *tr = tile + rows.off[r];
+        tr[0] = rows.weight[r];
+        double *rr = tr + 1, *aw = rr + rows.nref[r];
+        const int kind = rows.kind[r];
+        if (kind == AGX_RES_STATE) {
+          for (int i = 0; i < NV; ++i) { rr[i] = q[i]; rr[NV + i] = dq[i]; aw[i] = sp.w_q[i]; aw[NV + i] = sp.w_qdot[i]; }
+        } else if (kind == AGX_RES_CONTROL) {
+          for (int i = 0; i < NV; ++i) { rr[i] = u[i]; aw[i] = sp.w_effort[i]; }
+        } else if (kind == AGX_RES_FRAME_PLACEMENT) {
+          for (int e = 0; e < 9; ++e) rr[e] = RF[e];
+          for (int e = 0; e < 3; ++e) rr[9 + e] = pF[e];
+          for (int e = 0; e < 6; ++e) aw[e] = wp[e];
+        } else if (kind == AGX_RES_FRAME_TRANSLATION) {
+          for (int e = 0; e < 3; ++e) { rr[e] = pF[e]; aw[e] = wp[e]; }
+        } else if (kind == AGX_RES_FRAME_ROTATION) {
+          for (int e = 0; e < 9; ++e) rr[e] = RF[e];
+          for (int e = 0; e < 3; ++e) aw[e] = wp[3 + e];
+        } else {
+          if (kind == AGX_RES_COLLISION && sp.gw_item) tr[0] = sp.gw_item[src];
+          for (int e = 0; e < rows.nref[r] + rows.nr[r]; ++e) rr[e] = 0.0;
+        }
+      }
+    }
+  }
+}
+
 template <int NV, bool CHAIN>
 __global__ void k_sine_fill(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op, SineParams sp,
                             double *__restrict__ traj, double *__restrict__ pts) {
@@ -1902,7 +1966,7 @@ __global__ void k_sine_fill(const DevModel *__restrict__ mp, const DevOcp *__res
   if (unit >= (long long)o.B * sp.n_points) return;
   const int b = (int)(unit / sp.n_points), kk = (int)(unit % sp.n_points);
   const double t = sp.gq ? 0.0 : sp.t0[b] + kk * sp.dt;  // caller-given samples carry no time (and no t0 array)
-  double q[NV], dq[NV], ddq[NV], u[NV];
+  double q[NV], dq[NV], ddq[NV];
   if (sp.gq) {
 AGX_UNROLL_NV
     for (int i = 0; i < NV; ++i) { q[i] = sp.gq[unit * NV + i]; dq[i] = sp.gdq[unit * NV + i]; ddq[i] = sp.gddq[unit * NV + i]; }
@@ -1925,55 +1989,27 @@ AGX_UNROLL_NV
     dq[i] = A * (v5 * sw + p5 * w * cw);
     ddq[i] = A * (a5 * sw + 2.0 * v5 * w * cw - p5 * w * w * sw);
   }
-  Kin<NV> k;
-  kinematics<NV, CHAIN>(m, q, k);
-  rnea<NV, CHAIN>(m, k, dq, ddq, u);
-  double RF[9], pF[3];
-  int jf;
-  frame_world<NV>(m, k, sp.frame, RF, pF, &jf);
-  if (sp.gpose) {
-#pragma unroll
-    for (int e = 0; e < 9; ++e) RF[e] = sp.gpose[unit * 12 + e];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) pF[e] = sp.gpose[unit * 12 + 9 + e];
-  }
-  double *pt = pts + unit * (4 * NV + 12);
+  traj_sample_write<NV, CHAIN>(m, o, sp, unit, q, dq, ddq, traj, pts, unit, -1);
+}
+
+// Streamed resident trajectory (agx_traj_stream_append): the ring holds `cap` sample slots per instance followed by `mirror`
+// slots that repeat slots 0 .. mirror - 1 (sp.n_points = cap + mirror), so that every window of up to mirror + 1 samples is
+// contiguous from slot k0 mod cap.  One lane per (instance, new sample): sample j of the staged chunk [B][m] (sp.gq, ...) is logical
+// sample end + j and goes to slot (end + j) mod cap, and to cap + that slot when it has a mirror.
+template <int NV, bool CHAIN>
+__global__ void k_traj_append(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op, SineParams sp, double *__restrict__ traj,
+                              double *__restrict__ pts, int m_new, int end, int cap, int mirror) {
+  const DevModel &m = *mp;
+  const DevOcp &o = *op;
+  const long long unit = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (unit >= (long long)o.B * m_new) return;
+  const int b = (int)(unit / m_new), j = (int)(unit % m_new);
+  const int slot = (int)(((long long)end + j) % cap);
+  double q[NV], dq[NV], ddq[NV];
 AGX_UNROLL_NV
-  for (int i = 0; i < NV; ++i) { pt[i] = q[i]; pt[NV + i] = dq[i]; pt[2 * NV + i] = ddq[i]; pt[3 * NV + i] = u[i]; }
-AGX_UNROLL_NV
-  for (int e = 0; e < 9; ++e) pt[4 * NV + e] = RF[e];
-AGX_UNROLL_NV
-  for (int e = 0; e < 3; ++e) pt[4 * NV + 9 + e] = pF[e];
-  double wp[6];
-#pragma unroll
-  for (int e = 0; e < 6; ++e) wp[e] = sp.gw_pose ? sp.gw_pose[unit * 6 + e] : sp.w_pose[e];
-  for (int layout = 0; layout < 2; ++layout) {
-    const DevRows &rows = o.rows[layout];
-    double *tile = traj + unit * 2 * o.stride + layout * o.stride;
-    for (int r = 0; r < rows.n; ++r) {
-      double *tr = tile + rows.off[r];
-      tr[0] = rows.weight[r];
-      double *rr = tr + 1, *aw = rr + rows.nref[r];
-      const int kind = rows.kind[r];
-      if (kind == AGX_RES_STATE) {
-        for (int i = 0; i < NV; ++i) { rr[i] = q[i]; rr[NV + i] = dq[i]; aw[i] = sp.w_q[i]; aw[NV + i] = sp.w_qdot[i]; }
-      } else if (kind == AGX_RES_CONTROL) {
-        for (int i = 0; i < NV; ++i) { rr[i] = u[i]; aw[i] = sp.w_effort[i]; }
-      } else if (kind == AGX_RES_FRAME_PLACEMENT) {
-        for (int e = 0; e < 9; ++e) rr[e] = RF[e];
-        for (int e = 0; e < 3; ++e) rr[9 + e] = pF[e];
-        for (int e = 0; e < 6; ++e) aw[e] = wp[e];
-      } else if (kind == AGX_RES_FRAME_TRANSLATION) {
-        for (int e = 0; e < 3; ++e) { rr[e] = pF[e]; aw[e] = wp[e]; }
-      } else if (kind == AGX_RES_FRAME_ROTATION) {
-        for (int e = 0; e < 9; ++e) rr[e] = RF[e];
-        for (int e = 0; e < 3; ++e) aw[e] = wp[3 + e];
-      } else {
-        if (kind == AGX_RES_COLLISION && sp.gw_item) tr[0] = sp.gw_item[unit];
-        for (int e = 0; e < rows.nref[r] + rows.nr[r]; ++e) rr[e] = 0.0;
-      }
-    }
-  }
+  for (int i = 0; i < NV; ++i) { q[i] = sp.gq[unit * NV + i]; dq[i] = sp.gdq[unit * NV + i]; ddq[i] = sp.gddq[unit * NV + i]; }
+  const long long dst = (long long)b * sp.n_points + slot;
+  traj_sample_write<NV, CHAIN>(m, o, sp, unit, q, dq, ddq, traj, pts, dst, slot < mirror ? dst + cap : -1);
 }
 
 // Horizon window with non-uniform sample indexes (TrajectoryBuffer.horizon_indexes, trajectory.py:181-231:

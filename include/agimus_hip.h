@@ -335,7 +335,9 @@ int agx_ocp_qp_tiles(agx_ocp *ocp, double *qt, double *aux, int *qt_size, int *a
  * only, 6 = exit (gains) sweep alone, 7 = direction + speculative gains sweep in one launch,
  * 8 = the closed-loop rollout of agx_ocp_feedback_rollout as the handle would launch it (10 sub-steps of
  * 1 ms, no disturbance; with or without a plant), x0 restored afterwards, 9 = k_cost_pairs alone (wide cost sets; on
- * such a handle 0 and 3 time K1 and k_cost_pairs together, as every derivative pass launches them).             */
+ * such a handle 0 and 3 time K1 and k_cost_pairs together, as every derivative pass launches them),
+ * 10 = the device work of the last agx_traj_stream_append again (transfer of the staged chunk + fill of its slots with the
+ * same values), on the COPY stream, after the host has waited for both streams; the handle's state is left as it is.  */
 int agx_ocp_time_kernel(agx_ocp *ocp, int which, int reps, double *avg_ms);
 
 /* In-situ kernel timing: while enabled, every solve brackets the launches of its SQP loop with
@@ -397,6 +399,56 @@ int agx_traj_cartesian_sine_wi_create(agx_ocp *ocp, int n_points, double dt, con
                                       const double *pulsation, double scale_duration, double precision, int it_max,
                                       const double *w_q, const double *w_qdot, const double *w_effort, const double *w_pose,
                                       int frame, const double *period, double max_weight, double rate);
+/* ---- streamed resident trajectory ---------------------------------------------------------------------------------------
+ * The resident trajectory as TrajectoryBuffer uses it (trajectory.py:181-231: an unbounded list the planner appends to while
+ * MPC.run pops one point per step with clear_past, mpc.py:30-41): a RING of `capacity` samples per instance in HBM that the
+ * caller appends to and releases from while agx_ocp_mpc_step runs on it -- no allocation per step, no host wait for the solver,
+ * and the tile carry goes on.  Samples have LOGICAL indexes 0, 1, 2, ... (int, as in agx_ocp_mpc_step); the handle retains
+ * [first, end) with end - first <= capacity.  Logical sample k lives in slot k mod capacity and, when that slot is below
+ * max_span - 1, a second time in the mirror slot capacity + (k mod capacity), so every window of up to max_span samples is
+ * contiguous from slot k0 mod capacity and the window arithmetic, the gather of non-uniform horizons, the warm start and the
+ * readers work as on a one-shot trajectory.  On a streamed handle agx_traj_set_window, agx_ocp_mpc_step,
+ * agx_traj_warmstart_from_reference, agx_traj_get_point and agx_traj_get_tile take logical indexes and fail with a message
+ * naming [first, end) when the window or sample is not inside it; agx_traj_set_horizon_indexes refuses idx[T] + 1 > max_span.
+ *
+ * agx_traj_stream_create: like the other create calls it frees any earlier trajectory, ends the tile carry and makes the
+ * frame rows look at `frame`; it leaves an EMPTY ring (first = end = 0) and no window.  max_span: the most samples a window
+ * may cover (idx[T] + 1, T + 1 for uniform indexes).  Refuses max_span < T + 1, capacity < max_span, a bad frame and horizon
+ * indexes already set on the handle that are wider than max_span.  Every
+ * model size agx_traj_generic_create serves; joint weights [nv], w_pose [6] (used by appends without a w_pose array).    */
+int agx_traj_stream_create(agx_ocp *ocp, int capacity, int max_span, const double *w_q, const double *w_qdot,
+                           const double *w_effort, const double *w_pose, int frame);
+/* Appends logical samples end .. end + m - 1 of every instance: q, dq, ddq [B][m][nv]; pose [B][m][12], w_pose [B][m][6],
+ * w_collision [B][m] optional, meaning what they mean in agx_traj_generic_create_weighted (NULL: forward kinematics of the
+ * sample / the w_pose of create / the row's YAML weight).  Efforts by RNEA and poses by FK on the device, by the device
+ * function the one-shot generators use: the tiles are bit for bit those of agx_traj_generic_create_weighted on the same samples.
+ * Refuses m < 1, a ring that would overflow (release the past first), end + m beyond INT_MAX, non-finite input and a handle
+ * without a stream; a refused call changes nothing.
+ * Ordering contract.  The call copies the arrays into page-locked memory of the handle (the caller may reuse them on return)
+ * and enqueues, on the handle's COPY stream (the one agx_ocp_set_refs_async uses), the transfer and the fill of the slots.  The
+ * fill waits for an event recorded on the solver stream at the time of the call, so no work queued earlier can still be
+ * reading a released slot it overwrites; the host does not wait.  A later agx_traj_set_window / agx_ocp_mpc_step (or reader)
+ * that reaches a sample of an append not yet joined makes the SOLVER stream wait for that append's event -- again the host
+ * does not wait.  The host blocks only when it reuses a staging buffer whose fill has not finished: there are two, used in
+ * turn, each holding max_span samples per instance (a longer append goes in pieces).  Append and release do not end the tile
+ * carry: they touch only samples no earlier window contained.                                                            */
+int agx_traj_stream_append(agx_ocp *ocp, int m, const double *q, const double *dq, const double *ddq, const double *pose,
+                           const double *w_pose, const double *w_collision);
+/* Samples below k are no longer needed (TrajectoryBuffer.clear_past, several at once if wanted): first = k.  Refuses
+ * k < first and k > end.  No device work.                                                                                */
+int agx_traj_stream_release(agx_ocp *ocp, int k);
+/* The retained logical range [first, end) (either pointer may be NULL).                                                  */
+int agx_traj_stream_range(agx_ocp *ocp, int *first, int *end);
+/* The ordering contract as the host keeps it (a debug reader for tests): *joins = how often the solver stream has been made
+ * to wait for an append's event since the handle was created, *pending = appended pieces (0 .. 2) no window or reader has
+ * reached and no staging-buffer reuse has completed yet (either pointer may be NULL).                                    */
+int agx_traj_stream_joins(agx_ocp *ocp, long long *joins, int *pending);
+/* In-situ timing of the two streams, in the manner of agx_ocp_profile: while enabled, every join is bracketed by two hipEvents on
+ * the SOLVER stream -- ms_sum[0] / count[0]: how long that stream sat waiting for a fill, the event in front of the wait
+ * completing as soon as the stream reaches it -- and every appended piece by two on the COPY stream -- ms_sum[1] / count[1]:
+ * transfer + fill, the wait for the solver's event included.  Returns what has accumulated since timing was switched on (the
+ * host waits for both streams to read the events out); switching on or off clears the sums.                              */
+int agx_traj_stream_timing(agx_ocp *ocp, int enable, double *ms_sum, long long *count);
 /* Point the solver at the horizon window starting at sample `k0` of the
  * resident trajectory (TrajectoryBuffer.horizon, trajectory.py:218-222, with
  * uniform horizon indexes).                                                    */
