@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "agx_traj_cartesian_sine_create", "agx_ocp_set_refs_async", "agx_ocp_refs_activate", "agx_ocp_refs_wait", "agx_host_alloc", "agx_host_free",
     "agx_ocp_download_async", "agx_ocp_download_wait",
     "agx_traj_generic_create_weighted", "agx_traj_cartesian_sine_wi_create", "agx_traj_get_tile",
-    "agx_ocp_set_plant_inertials", "agx_model_sensitivity", "agx_ocp_cost_wide",
+    "agx_ocp_set_plant_inertials", "agx_model_sensitivity", "agx_ocp_cost_wide", "agx_ocp_set_model_inertials",
     "agx_traj_stream_create", "agx_traj_stream_append", "agx_traj_stream_release", "agx_traj_stream_range",
     "agx_traj_stream_joins", "agx_traj_stream_timing",
 ]  # fmt: skip
@@ -581,6 +581,20 @@ class HipOcp:
     def clear_plant_inertials(self):
         """feedback_rollout simulates the controller's own model again."""
         _chk(lib().agx_ocp_set_plant_inertials(self._h, None, None, None, None))
+
+    # -- controller model per instance -------------------------------------------
+    def set_model_inertials(self, mass, com, inertia, armature=None):
+        """Per-instance link inertials of the model instance b SOLVES with (`workloads.stack_inertials` of B tables), arrays as
+        `set_plant_inertials`.  Derivative passes, the warm-start shift and -- with no plant set -- feedback_rollout read them;
+        integrate, rnea, the frame functions, model_sensitivity and the trajectory generators keep the model's own table.
+        Models of at most 7 joints after padding, no ControlGrav item."""
+        mass, com, inertia = self._plant_arg("mass", mass, ()), self._plant_arg("com", com, (3,)), self._plant_arg("inertia", inertia, (9,))
+        arm = None if armature is None else self._plant_arg("armature", armature, ())
+        _chk(lib().agx_ocp_set_model_inertials(self._h, _p(mass), _p(com), _p(inertia), _p(arm)))
+
+    def clear_model_inertials(self):
+        """Every instance solves with the model's own table again."""
+        _chk(lib().agx_ocp_set_model_inertials(self._h, None, None, None, None))
 
     def model_sensitivity(self, x, u, dt, delta_inertia=0.01, delta_com=0.01, delta_mass=0.01):
         """[n][2 nv][10 nv] sensitivity of the Euler node's next state to the link inertials of the controller's model at the

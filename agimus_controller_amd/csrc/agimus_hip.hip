@@ -161,6 +161,11 @@ struct agx_ocp {
   double *d_plant = nullptr;
   bool plant_set = false;
   std::vector<double> plant_stage;  // host image of d_plant (the upload reads it after the setter has returned the caller's arrays)
+  // per-instance controller model (agx_ocp_set_model_inertials, 7-joint capacity): agx::InstanceInertials<nv>[B].  While set,
+  // launch_k1, launch_calc_diff_rows, the warm-start shift and the plant-less rollout launch the instantiations that read it.
+  double *d_minert = nullptr;
+  bool minert_set = false;
+  std::vector<double> minert_stage;
   RefView rv{};
   // resident trajectory
   double *d_traj = nullptr, *d_pts = nullptr;
@@ -516,7 +521,13 @@ int launch_calc_diff_rows(agx_ocp *o, bool masked, bool running_only) {
     constexpr bool CH = decltype(CHc)::value;
     const long long units = (long long)o->B * o->T;
     const int grid = (int)((units + 63) / 64);
+    // per-instance controller inertials: the running nodes from the instantiations that read them (terminal nodes carry costs only)
+    [[maybe_unused]] const auto *inst = (const agx::InstanceInertials<NV> *)o->d_minert;
     if constexpr (NV <= 7) if (o->general) {
+      if (o->minert_set)
+        hipLaunchKernelGGL((agx::k_calc_diff<NV, CH, true>), dim3(grid), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
+                           o->d_us, o->rv, o->d_tiles, masked ? o->d_state : nullptr, inst);
+      else
       hipLaunchKernelGGL((agx::k_calc_diff<NV, CH, true>), dim3(grid), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
                          o->d_us, o->rv, o->d_tiles, masked ? o->d_state : nullptr);
       if (running_only) { HIPCHK(hipGetLastError()); return 0; }
@@ -525,6 +536,11 @@ int launch_calc_diff_rows(agx_ocp *o, bool masked, bool running_only) {
       HIPCHK(hipGetLastError());
       return 0;
     }
+    const bool with_inst = NV <= 7 && o->minert_set;  // (the larger capacities have no such instantiation: the setter refuses them)
+    if constexpr (NV <= 7) if (with_inst)
+      hipLaunchKernelGGL((agx::k_calc_diff<NV, CH>), dim3(grid), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
+                         o->d_us, o->rv, o->d_tiles, masked ? o->d_state : nullptr, inst);
+    if (!with_inst)
     hipLaunchKernelGGL((agx::k_calc_diff<NV, CH>), dim3(grid), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
                        o->d_us, o->rv, o->d_tiles, masked ? o->d_state : nullptr);
     if (running_only) { HIPCHK(hipGetLastError()); return 0; }
@@ -547,8 +563,14 @@ int launch_k1(agx_ocp *o, bool running_only, bool term_only, int phase, bool com
     const long long units = (long long)o->B * o->T;
     const double *xs_in = phase ? o->d_xs + (size_t)o->B * (o->T + 1) * o->nx : o->d_xs;
     const double *us_in = phase ? o->d_us + (size_t)o->B * o->T * o->nu : o->d_us;
+    // per-instance controller inertials (agx_ocp_set_model_inertials): the running nodes go to the instantiations that read
+    // them; the terminal kernels evaluate costs only and are today's
+    [[maybe_unused]] const auto *inst = (const agx::InstanceInertials<NV> *)o->d_minert;
     if constexpr (NV <= 7) if (o->general) {
-      if (!term_only)
+      if (!term_only && o->minert_set)
+        hipLaunchKernelGGL((agx::k_calc_qp<NV, CH, true>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
+                           o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, o->d_auxg, phase, inst);
+      else if (!term_only)
         hipLaunchKernelGGL((agx::k_calc_qp<NV, CH, true>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
                            o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, o->d_auxg, phase);
       if (!running_only)
@@ -565,10 +587,17 @@ int launch_k1(agx_ocp *o, bool running_only, bool term_only, int phase, bool com
 #define AGX_LAUNCH_LJ(COLL)                                                                                                              \
   do {                                                                                                                                   \
     if (o->k1_fused && !term_only && !running_only) { /* both node types in one launch */                                                \
+      if (o->minert_set)                                                                                                                 \
+        hipLaunchKernelGGL((agx::k_calc_qp_lj_all<NV, COLL>), dim3(n_run + n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1,     \
+                           o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, n_run, phase, cp, inst);                        \
+      else                                                                                                                               \
       hipLaunchKernelGGL((agx::k_calc_qp_lj_all<NV, COLL>), dim3(n_run + n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1, o->d_dt, \
                          xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, n_run, phase, cp);                                         \
     } else {                                                                                                                             \
-      if (!term_only)                                                                                                                    \
+      if (!term_only && o->minert_set)                                                                                                   \
+        hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, false, COLL>), dim3(n_run), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1, o->d_dt,     \
+                           xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp, inst);                                        \
+      else if (!term_only)                                                                                                               \
         hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, false, COLL>), dim3(n_run), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1, o->d_dt,     \
                            xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp);                                              \
       if (!running_only)                                                                                                                 \
@@ -590,7 +619,10 @@ int launch_k1(agx_ocp *o, bool running_only, bool term_only, int phase, bool com
                          us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase);
       });
     } else if (!lanes) {
-      if (!term_only)
+      if (!term_only && o->minert_set)
+        hipLaunchKernelGGL((agx::k_calc_qp<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
+                           o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, (double *)nullptr, phase, inst);
+      else if (!term_only)
         hipLaunchKernelGGL((agx::k_calc_qp<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
                            o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, (double *)nullptr, phase);
       if (!running_only)
@@ -764,14 +796,16 @@ int reset_state(agx_ocp *o) {
   return 0;
 }
 
-// the rollout the handle's plant asks for: k_feedback_rollout on the controller's own model, k_plant_rollout once a plant is set
+// the rollout the handle's plant asks for: k_plant_rollout on the plant's inertials once a plant is set; otherwise the
+// controller's model is its own plant: k_plant_rollout on its per-instance inertials if it has them, else k_feedback_rollout
 int launch_rollout(agx_ocp *o, int n_substeps, double dt_sub, const double *d_dist) {
   return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
-    if (o->plant_set)
+    if (o->plant_set || o->minert_set)
       hipLaunchKernelGGL((agx::k_plant_rollout<NV, CH>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model,
-                         (const agx::PlantInertials<NV> *)o->d_plant, o->d_us, o->d_Kout, o->d_x0, d_dist, o->B, o->T, n_substeps, dt_sub);
+                         (const agx::PlantInertials<NV> *)(o->plant_set ? o->d_plant : o->d_minert), o->d_us, o->d_Kout, o->d_x0, d_dist, o->B, o->T,
+                         n_substeps, dt_sub);
     else
       hipLaunchKernelGGL((agx::k_feedback_rollout<NV, CH>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model, o->d_us, o->d_Kout, o->d_x0,
                          d_dist, o->B, o->T, n_substeps, dt_sub);
@@ -1747,7 +1781,7 @@ void agx_ocp_destroy(agx_ocp *o) {
   if (o->copy_stream) (void)hipStreamSynchronize(o->copy_stream);
   void *ptrs[] = {o->d_mx2_elem, o->d_mx2_bnd, o->d_mx2_cl, o->d_ref_back, o->d_frames_back, o->d_snap, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us, o->d_x0, o->d_tiles, o->d_Kws, o->d_kws, o->d_Kout, o->d_dx,
                   o->d_du, o->d_ref, o->d_frames, o->d_state, o->d_ndone, o->d_scratch, o->d_traj, o->d_pts, o->d_sine, o->d_qt, o->d_aux, o->d_w, o->d_nodestat,
-                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr, o->d_plant, o->d_cw};
+                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr, o->d_plant, o->d_minert, o->d_cw};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (o->h_ndone) (void)hipHostFree(o->h_ndone);
@@ -2119,7 +2153,10 @@ int agx_ocp_shift_warmstart(agx_ocp *o) {
         hipLaunchKernelGGL((agx::k_integrate_wg<NV, decltype(PRc)::value>), dim3(o->B * (int)o->shift_nodes.size()), dim3(256), 0, o->stream, o->d_model, o->dt[0], o->d_xs,
                            o->d_us, o->d_xs + n, o->d_shift_nodes, (int)o->shift_nodes.size(), o->T);
       });
-    } else
+    } else if (o->minert_set)  // the re-integrated nodes follow the instance's own model
+      hipLaunchKernelGGL((agx::k_shift<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us,
+                         (const agx::InstanceInertials<NV> *)o->d_minert);
+    else
     hipLaunchKernelGGL((agx::k_shift<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us);
     hipLaunchKernelGGL(agx::k_shift_commit, dim3((int)((n + 255) / 256)), dim3(256), 0, o->stream, o->d_xs, o->d_us, o->B, o->T, o->nx, o->nu);
     HIPCHK(hipGetLastError());
@@ -2811,33 +2848,31 @@ int agx_ocp_feedback_rollout(agx_ocp *o, int n_substeps, double dt_sub, const do
   return 0;
 }
 
-int agx_ocp_set_plant_inertials(agx_ocp *o, const double *mass, const double *com, const double *inertia, const double *armature) {
-  if (!o) return fail("null handle");
-  if (!mass && !com && !inertia && !armature) {  // back to the controller's own model; d_plant stays allocated for the next plant
-    o->plant_set = false;
-    return 0;
-  }
-  if (!mass || !com || !inertia) return fail("agx_ocp_set_plant_inertials: mass, com and inertia go together (all NULL clears the plant)");
-  const size_t B = o->B, nv = o->nv, nvu = o->nvu, w = 14 * nv;  // agx::PlantInertials<nv>: mass nv | com 3 nv | inertia 9 nv | armature nv
+// The body of the two per-instance inertial setters: checks the caller's arrays (at nvu joints), builds the host image of
+// agx::InstanceInertials<nv>[B] in `stage` and uploads it to *d_buf (allocated on first use).  `fn` prefixes the messages.
+// Nothing of the handle changes unless every check has passed.
+static int upload_inertials(agx_ocp *o, const std::string &fn, const double *mass, const double *com, const double *inertia, const double *armature,
+                            std::vector<double> &stage, double **d_buf) {
+  const size_t B = o->B, nv = o->nv, nvu = o->nvu, w = 14 * nv;  // mass nv | com 3 nv | inertia 9 nv | armature nv
   for (size_t k = 0; k < B * nvu; ++k) {
     if (!std::isfinite(mass[k]) || (armature && !std::isfinite(armature[k])))
-      return fail("agx_ocp_set_plant_inertials: non-finite mass or armature (instance " + std::to_string(k / nvu) + ", joint " + std::to_string(k % nvu) + ")");
-    if (mass[k] < 0.0) return fail("agx_ocp_set_plant_inertials: negative mass (instance " + std::to_string(k / nvu) + ", joint " + std::to_string(k % nvu) + ")");
+      return fail(fn + ": non-finite mass or armature (instance " + std::to_string(k / nvu) + ", joint " + std::to_string(k % nvu) + ")");
+    if (mass[k] < 0.0) return fail(fn + ": negative mass (instance " + std::to_string(k / nvu) + ", joint " + std::to_string(k % nvu) + ")");
     if (armature && armature[k] < 0.0)
-      return fail("agx_ocp_set_plant_inertials: negative armature (instance " + std::to_string(k / nvu) + ", joint " + std::to_string(k % nvu) + ")");
+      return fail(fn + ": negative armature (instance " + std::to_string(k / nvu) + ", joint " + std::to_string(k % nvu) + ")");
   }
   for (size_t k = 0; k < B * nvu * 3; ++k)
-    if (!std::isfinite(com[k])) return fail("agx_ocp_set_plant_inertials: non-finite com (instance " + std::to_string(k / (3 * nvu)) + ")");
+    if (!std::isfinite(com[k])) return fail(fn + ": non-finite com (instance " + std::to_string(k / (3 * nvu)) + ")");
   for (size_t k = 0; k < B * nvu * 9; ++k)
-    if (!std::isfinite(inertia[k])) return fail("agx_ocp_set_plant_inertials: non-finite inertia (instance " + std::to_string(k / (9 * nvu)) + ")");
+    if (!std::isfinite(inertia[k])) return fail(fn + ": non-finite inertia (instance " + std::to_string(k / (9 * nvu)) + ")");
   if (set_device(o)) return -1;
-  if (!o->d_plant) HIPCHK(hipMalloc((void **)&o->d_plant, sizeof(double) * B * w));
-  // a rollout queued earlier may still read d_plant, and the copy below reads plant_stage: both are the handle's own, so the
+  if (!*d_buf) HIPCHK(hipMalloc((void **)d_buf, sizeof(double) * B * w));
+  // a kernel queued earlier may still read the buffer, and the copy below reads the image: both are the handle's own, so the
   // host waits for the stream before it rewrites the image, then uploads IN the solver's stream, behind everything queued
   HIPCHK(hipStreamSynchronize(o->stream));
-  o->plant_stage.assign(B * w, 0.0);
+  stage.assign(B * w, 0.0);
   for (size_t b = 0; b < B; ++b) {
-    double *p = o->plant_stage.data() + b * w, *pc = p + nv, *pi = pc + 3 * nv, *pa = pi + 9 * nv;
+    double *p = stage.data() + b * w, *pc = p + nv, *pi = pc + 3 * nv, *pa = pi + 9 * nv;
     for (size_t i = 0; i < nvu; ++i) {
       p[i] = mass[b * nvu + i];
       std::memcpy(pc + 3 * i, com + (b * nvu + i) * 3, sizeof(double) * 3);
@@ -2846,9 +2881,51 @@ int agx_ocp_set_plant_inertials(agx_ocp *o, const double *mass, const double *co
     }
     for (size_t i = nvu; i < nv; ++i) pa[i] = o->hm.armature[i];  // pad joints: massless, the armature of the padding
   }
-  HIPCHK(hipMemcpyAsync(o->d_plant, o->plant_stage.data(), sizeof(double) * B * w, hipMemcpyHostToDevice, o->stream));
+  HIPCHK(hipMemcpyAsync(*d_buf, stage.data(), sizeof(double) * B * w, hipMemcpyHostToDevice, o->stream));
   HIPCHK(hipStreamSynchronize(o->stream));
+  return 0;
+}
+
+int agx_ocp_set_plant_inertials(agx_ocp *o, const double *mass, const double *com, const double *inertia, const double *armature) {
+  if (!o) return fail("null handle");
+  if (!mass && !com && !inertia && !armature) {  // back to the controller's own model; d_plant stays allocated for the next plant
+    o->plant_set = false;
+    return 0;
+  }
+  if (!mass || !com || !inertia) return fail("agx_ocp_set_plant_inertials: mass, com and inertia go together (all NULL clears the plant)");
+  if (upload_inertials(o, "agx_ocp_set_plant_inertials", mass, com, inertia, armature, o->plant_stage, &o->d_plant)) return -1;
   o->plant_set = true;
+  return 0;
+}
+
+int agx_ocp_set_model_inertials(agx_ocp *o, const double *mass, const double *com, const double *inertia, const double *armature) {
+  if (!o) return fail("null handle");
+  if (!mass && !com && !inertia && !armature) {  // back to the nominal table; d_minert stays allocated for the next upload
+    if (!o->minert_set) return 0;
+    if (set_device(o)) return -1;
+    if (carry_invalidate(o)) return -1;
+    o->minert_set = false;
+    return 0;
+  }
+  if (!mass || !com || !inertia) return fail("agx_ocp_set_model_inertials: mass, com and inertia go together (all NULL goes back to the model's table)");
+  if (o->nv > 7)
+    return fail("agx_ocp_set_model_inertials: per-instance controller inertials are implemented for models of at most 7 joints after padding (this handle runs at " +
+                std::to_string(o->nv) + ")");
+  // g(q) of a ControlGrav row depends on the inertials and is evaluated on the model's table: refused, never silently nominal
+  // (whether the row is active or not: rows are switched on and off after creation)
+  for (int lay = 0; lay < 2; ++lay) {
+    for (int r = 0; r < o->ho.rows[lay].n; ++r)
+      if (o->ho.rows[lay].kind[r] == AGX_RES_CONTROL_GRAV)
+        return fail("agx_ocp_set_model_inertials: the problem has a ControlGrav cost item (" + std::string(lay ? "terminal" : "running") + " row " + std::to_string(r) +
+                    "), whose gravity torque is evaluated on the model's own table");
+    for (int r = 0; r < o->ho.cons[lay].n; ++r)
+      if (o->ho.cons[lay].kind[r] == AGX_RES_CONTROL_GRAV)
+        return fail("agx_ocp_set_model_inertials: the problem has a ControlGrav constraint item (" + std::string(lay ? "terminal" : "running") + " row " +
+                    std::to_string(r) + "), whose gravity torque is evaluated on the model's own table");
+  }
+  if (upload_inertials(o, "agx_ocp_set_model_inertials", mass, com, inertia, armature, o->minert_stage, &o->d_minert)) return -1;
+  if (carry_invalidate(o)) return -1;  // every tile depends on the inertials; they are constant across steps, so the carry resumes
+  o->minert_set = true;
   return 0;
 }
 
@@ -2903,6 +2980,11 @@ int agx_ocp_mpc_step(agx_ocp *o, int k0, int max_iter, int first) {
         constexpr int NV = decltype(NVc)::value;
         constexpr bool CH = decltype(CHc)::value;
         if constexpr (NV <= 8) {
+          if (o->minert_set)
+            hipLaunchKernelGGL((agx::k_mpc_prologue<NV, CH>), dim3(o->B), dim3(128), lds, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
+                               o->d_us, o->d_x0, o->d_state, o->d_ndone, first == 0 ? 1 : 0, carry ? 1 : 0, o->head,
+                               (int *)((char *)o->d_ocp + offsetof(DevOcp, head)), (const agx::InstanceInertials<NV> *)o->d_minert);
+          else
           hipLaunchKernelGGL((agx::k_mpc_prologue<NV, CH>), dim3(o->B), dim3(128), lds, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
                              o->d_us, o->d_x0, o->d_state, o->d_ndone, first == 0 ? 1 : 0, carry ? 1 : 0, o->head,
                              (int *)((char *)o->d_ocp + offsetof(DevOcp, head)));

@@ -405,15 +405,17 @@ AGX_UNROLL_NV
 
 // ------------------------------------------------------------------ other inertial sources
 // body_inertia / bias_and_inertia above read a link's inertials from the model's own table, and every kernel of the solver
-// calls those.  The overloads below take them from a source instead: the plant of the closed loop from PlantInertials[b] of
-// its instance, the sensitivity sweep from the model with one entry moved (PerturbedInertials, agx_kernels.hpp).  A source
-// gives mass_of(i), com_of(i, e), inertia_of(i, e) (row major, about the com, joint frame) and armature_of(i); the kinematic
-// tree, the axes and gravity are always the model's.  The arithmetic is that of the routines above, operation for operation.
+// calls those unless its handle has per-instance controller inertials.  The overloads below take them from a source instead:
+// the plant of the closed loop and the per-instance controller model from InstanceInertials[b] of their instance, the
+// sensitivity sweep from the model with one entry moved (PerturbedInertials, agx_kernels.hpp).  A source gives mass_of(i),
+// com_of(i, e), inertia_of(i, e) (row major, about the com, joint frame) and armature_of(i); the kinematic tree, the axes
+// and gravity are always the model's.  The arithmetic is that of the routines above, operation for operation.
 
-// Inertials of ONE plant instance at the compiled capacity NV, laid out as the model's table (RobotTable / DevModel): the pad
-// joints of a model below the capacity are massless and carry the armature the padding gives them.
+// Inertials of ONE instance at the compiled capacity NV, laid out as the model's table (RobotTable / DevModel): the pad joints of
+// a model below the capacity are massless and carry the armature the padding gives them.  Two tables of them can hang on a
+// handle: the plant of the closed loop (agx_ocp_set_plant_inertials) and the controller's model (agx_ocp_set_model_inertials).
 template <int NV>
-struct PlantInertials {
+struct InstanceInertials {
   double mass[NV];
   double com[NV][3];
   double inertia[NV][9];
@@ -423,6 +425,8 @@ struct PlantInertials {
   AGX_DEV double inertia_of(int i, int e) const { return inertia[i][e]; }
   AGX_DEV double armature_of(int i) const { return armature[i]; }
 };
+template <int NV>
+using PlantInertials = InstanceInertials<NV>;
 
 template <int NV, class INERTIALS>
 AGX_DEV void body_inertia(const INERTIALS &in, const Kin<NV> &k, int i, double *I) {

@@ -111,12 +111,20 @@ struct LjModel {
 // COLL: the row table may hold ONE ResidualDistanceCollision cost row (closest points of the pair evaluated redundantly by
 // the 8 lanes of the node, lane j its own column of the distance gradient); a template flag because the narrow-phase code
 // would otherwise cost the collision-free kernel registers.
-template <int NV, bool TERM, bool COLL = false>
+// PINST: the inertial part of the joint constants (com 3 | inertia 9 | mass | armature) is the node's own: lane j loads the 14
+// doubles of ITS joint from inst[b], the per-instance controller model of the node's instance (agx_ocp_set_model_inertials).
+// The eight nodes of a wave can belong to several instances, so this part cannot be staged per wave; placement and axis still
+// come from lmod.  The loads sit right in front of their only uses (the world-frame body inertia; the armature on the diagonal
+// of M), after the cost phase, so that they add nothing to the long live ranges.  Only running nodes read inertials: a terminal
+// node carries costs alone (Ib, Ic and m6 below are dead under TERM), so the callers never set PINST together with TERM.
+template <int NV, bool TERM, bool COLL = false, bool PINST = false>
 __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds, LjModel &lmod, const DevModel *__restrict__ mp,
                                                 const DevOcp *__restrict__ op, const double *__restrict__ dts,
                                                 const double *__restrict__ xs, const double *__restrict__ us, const RefView &rv,
                                                 double *__restrict__ qts, double *__restrict__ auxs,
-                                                const DevState *__restrict__ st, const int phase, const int compact) {
+                                                const DevState *__restrict__ st, const int phase, const int compact,
+                                                const InstanceInertials<NV> *__restrict__ inst = nullptr) {
+  static_assert(!(PINST && TERM), "terminal nodes read no inertials");
   constexpr int NX = 2 * NV;
   typedef QT<NV> Q;
   typedef AUX<NV> A;
@@ -408,13 +416,23 @@ __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds
 
   // body inertia in the world frame
   double Ib[10];
+  [[maybe_unused]] double pin[14];  // PINST: com 3 | inertia 9 | mass | armature of this lane's joint in the node's instance
+  if constexpr (PINST) {
+    const InstanceInertials<NV> &in = inst[b];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) pin[e] = in.com[j][e];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) pin[3 + e] = in.inertia[j][e];
+    pin[12] = in.mass[j];
+    pin[13] = in.armature[j];
+  }
   {
     double cw[3];
-    mv3(R, mj + 15, cw);
+    mv3(R, PINST ? pin : mj + 15, cw);
     cw[0] += p[0]; cw[1] += p[1]; cw[2] += p[2];
-    const double ms = jl ? mj[27] : 0.0;
+    const double ms = jl ? (PINST ? pin[12] : mj[27]) : 0.0;
     double Tm[9], Iw[9];
-    mm3(R, mj + 18, Tm);
+    mm3(R, PINST ? pin + 3 : mj + 18, Tm);
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -470,7 +488,7 @@ __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds
       double val;
       if (i >= l8) val = dot6(S, L.u.d1.m6[i]);
       else val = dot6(L.u.d1.S[i], m6);
-      if (i == l8) val += mj[28];
+      if (i == l8) val += PINST ? pin[13] : mj[28];
       Mc[i] = val;
       L.M[i][l8] = val;
     }
@@ -689,29 +707,33 @@ __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds
 }
 
 // Separate launches (timing, terminal-only / running-only callers)
-template <int NV, bool TERM, bool COLL = false>
+// INST: empty, or InstanceInertials<NV> with one more argument, the per-instance controller model (PINST of the body) -- the
+// kernel with the pack empty is today's, argument for argument.
+template <int NV, bool TERM, bool COLL = false, class... INST>
 __global__ void __launch_bounds__(64, AGX_K1_WAVES) k_calc_qp_lj(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                     const double *__restrict__ dts, const double *__restrict__ xs,
                                                     const double *__restrict__ us, RefView rv, double *__restrict__ qts,
-                                                    double *__restrict__ auxs, const DevState *__restrict__ st, int phase, int compact) {
+                                                    double *__restrict__ auxs, const DevState *__restrict__ st, int phase, int compact,
+                                                    const INST *__restrict__... inst) {
+  static_assert(!(TERM && sizeof...(INST) > 0), "terminal nodes read no inertials: launch the kernel without them");
   __shared__ LjNode lds[8];  // one wave per workgroup: 8 nodes
   __shared__ LjModel lmod;
-  calc_qp_lj_body<NV, TERM, COLL>(blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact);
+  calc_qp_lj_body<NV, TERM, COLL, (sizeof...(INST) > 0)>(blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact, inst...);
 }
 
 // The derivative pass of one SQP iteration in ONE launch: the first n_run workgroups take the running
 // nodes, the rest the terminal nodes (wave-uniform branch, shared LDS declarations): the short
 // terminal launch and its dispatch gap disappear behind the tail of the running nodes.
-template <int NV, bool COLL = false>
+template <int NV, bool COLL = false, class... INST>
 __global__ void __launch_bounds__(64, AGX_K1_WAVES) k_calc_qp_lj_all(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                         const double *__restrict__ dts, const double *__restrict__ xs,
                                                         const double *__restrict__ us, RefView rv, double *__restrict__ qts,
                                                         double *__restrict__ auxs, const DevState *__restrict__ st, int n_run,
-                                                        int phase, int compact) {
+                                                        int phase, int compact, const INST *__restrict__... inst) {
   __shared__ LjNode lds[8];
   __shared__ LjModel lmod;
   if ((int)blockIdx.x < n_run)
-    calc_qp_lj_body<NV, false, COLL>(blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact);
+    calc_qp_lj_body<NV, false, COLL, (sizeof...(INST) > 0)>(blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact, inst...);
   else
     calc_qp_lj_body<NV, true, COLL>((long long)blockIdx.x - n_run, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact);
 }

@@ -33,11 +33,16 @@ __device__ __forceinline__ void count_carriable(DevState &S, int *n_done) {
 // ---------------------------------------------------------------------------
 // K1: derivative pass over the running nodes.  unit = b*T + t, one lane each.
 // ---------------------------------------------------------------------------
-template <int NV, bool CHAIN, bool GEN = false>
+// INST (here and in the other one-lane kernels): empty, or InstanceInertials<NV> with one more argument, the per-instance
+// inertials of the controller's model (agx_ocp_set_model_inertials): instance b then takes mass, centre of mass, inertia and
+// armature of every link from inst[b] through the source overloads of agx_device.hpp.  With the pack empty the kernel is,
+// argument for argument and line for line, the one on the model's own table.
+template <int NV, bool CHAIN, bool GEN = false, class... INST>
 __global__ void __launch_bounds__(64) k_calc_diff(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                   const double *__restrict__ dts, const double *__restrict__ xs,
                                                   const double *__restrict__ us, RefView rv,
-                                                  double *__restrict__ tiles, const DevState *__restrict__ st) {
+                                                  double *__restrict__ tiles, const DevState *__restrict__ st,
+                                                  const INST *__restrict__... inst) {
   constexpr int NX = 2 * NV, NU = NV;
   typedef TileOff<NV> TO;
   const DevModel &m = *mp;
@@ -61,7 +66,8 @@ __global__ void __launch_bounds__(64) k_calc_diff(const DevModel *__restrict__ m
   kinematics<NV, CHAIN>(m, x, k);
   Dyn<NV> d;
   double nle[NV], M[NV][NV], Minv[NV][NV], qdd[NV];
-  bias_and_inertia<NV, CHAIN>(m, k, x + NV, d, nle, M);
+  if constexpr (sizeof...(INST) == 0) bias_and_inertia<NV, CHAIN>(m, k, x + NV, d, nle, M);
+  else bias_and_inertia<NV, CHAIN>(m, inst[b]..., k, x + NV, d, nle, M);
   spd_inverse<NV>(M, Minv);
 AGX_UNROLL_NV
   for (int i = 0; i < NV; ++i) {
@@ -197,12 +203,12 @@ AGX_UNROLL_NV
 // Every NV x NV block is stored with a row stride of LD = 8 doubles: a row is one aligned 64-byte
 // line, so the column-per-lane kernels write whole lines and the 8 x 8 lane grid of the Riccati
 // kernel reads element [r][c] of a block at offset 8 r + c = its own lane id (one 512-byte load).
-template <int NV, bool CHAIN, bool GEN = false>
+template <int NV, bool CHAIN, bool GEN = false, class... INST>
 __device__ __forceinline__ void calc_qp_body(const long long unit, const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                              const double *__restrict__ dts, const double *__restrict__ xs,
                                              const double *__restrict__ us, const RefView &rv, double *__restrict__ qts,
                                              double *__restrict__ auxs, const DevState *__restrict__ st,
-                                             double *__restrict__ auxg = nullptr, int phase = 0) {
+                                             double *__restrict__ auxg = nullptr, int phase = 0, const INST *__restrict__... inst) {
   constexpr int NX = 2 * NV, NU = NV;
   typedef QT<NV> Q;
   typedef AUX<NV> A;
@@ -228,7 +234,8 @@ __device__ __forceinline__ void calc_qp_body(const long long unit, const DevMode
   kinematics<NV, CHAIN>(m, x, k);
   Dyn<NV> d;
   double nle[NV], M[NV][NV], L[NV][NV], Minv[NV][NV], qdd[NV];
-  bias_and_inertia<NV, CHAIN>(m, k, x + NV, d, nle, M);
+  if constexpr (sizeof...(INST) == 0) bias_and_inertia<NV, CHAIN>(m, k, x + NV, d, nle, M);
+  else bias_and_inertia<NV, CHAIN>(m, inst[b]..., k, x + NV, d, nle, M);
 AGX_UNROLL_NV
   for (int i = 0; i < NV; ++i)
 #pragma unroll
@@ -326,13 +333,13 @@ AGX_UNROLL_NV
   }
 }
 
-template <int NV, bool CHAIN, bool GEN = false>
+template <int NV, bool CHAIN, bool GEN = false, class... INST>
 __global__ void __launch_bounds__(64) k_calc_qp(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                 const double *__restrict__ dts, const double *__restrict__ xs,
                                                 const double *__restrict__ us, RefView rv, double *__restrict__ qts,
                                                 double *__restrict__ auxs, const DevState *__restrict__ st,
-                                                double *__restrict__ auxg = nullptr, int phase = 0) {
-  calc_qp_body<NV, CHAIN, GEN>((long long)blockIdx.x * blockDim.x + threadIdx.x, mp, op, dts, xs, us, rv, qts, auxs, st, auxg, phase);
+                                                double *__restrict__ auxg = nullptr, int phase = 0, const INST *__restrict__... inst) {
+  calc_qp_body<NV, CHAIN, GEN>((long long)blockIdx.x * blockDim.x + threadIdx.x, mp, op, dts, xs, us, rv, qts, auxs, st, auxg, phase, inst...);
 }
 
 template <int NV, bool CHAIN, bool GEN = false>
@@ -1234,12 +1241,44 @@ __global__ void k_x0_from_pred(double *x0, const double *xs, int B, int T, int N
   x0[i] = xs[((long long)b * (T + 1) + 1) * NX + e];
 }
 
+// Joint accelerations of the model's kinematic tree carrying the inertials of `in`: the forward dynamics of
+// node_calc_running (world-frame bias torques and joint-space inertia, explicit inverse) with another inertial source.
+template <int NV, bool CHAIN, class INERTIALS>
+AGX_DEV void forward_dynamics_with(const DevModel &m, const INERTIALS &in, const double *x, const double *u, double *a) {
+  Kin<NV> k;
+  kinematics<NV, CHAIN>(m, x, k);
+  Dyn<NV> d;
+  double nle[NV], M[NV][NV], Minv[NV][NV];
+  bias_and_inertia<NV, CHAIN>(m, in, k, x + NV, d, nle, M);
+  spd_inverse<NV>(M, Minv);
+AGX_UNROLL_NV
+  for (int i = 0; i < NV; ++i) {
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc += Minv[i][j] * (u[j] - nle[j]);
+    a[i] = acc;
+  }
+}
+
+// One semi-implicit Euler node on those accelerations: the update of node_calc_running, operation for operation.
+template <int NV, bool CHAIN, class INERTIALS>
+AGX_DEV void euler_node_with(const DevModel &m, const INERTIALS &in, double dt, const double *x, const double *u, double *xnext) {
+  double a[NV];
+  forward_dynamics_with<NV, CHAIN>(m, in, x, u, a);
+AGX_UNROLL_NV
+  for (int i = 0; i < NV; ++i) {
+    xnext[NV + i] = x[NV + i] + dt * a[i];
+    xnext[i] = x[i] + dt * x[NV + i] + dt * dt * a[i];
+  }
+}
+
 // WarmStartShiftPreviousSolution.shift (warm_start_shift_previous_solution.py:85-109):
 // one lane per instance walks the horizon in order (the update is sequential in i
 // because xs[i] <- xs[i+1] reads the not-yet-shifted neighbour).
-template <int NV, bool CHAIN>
+// INST: as k_calc_diff -- the re-integrated nodes of instance b follow the dynamics of inst[b].
+template <int NV, bool CHAIN, class... INST>
 __global__ void k_shift(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op, const double *__restrict__ dts,
-                        double *__restrict__ xs, double *__restrict__ us) {
+                        double *__restrict__ xs, double *__restrict__ us, const INST *__restrict__... inst) {
   constexpr int NX = 2 * NV, NU = NV;
   const DevModel &m = *mp;
   const DevOcp &o = *op;
@@ -1267,7 +1306,8 @@ AGX_UNROLL_NV
       for (int e = 0; e < NU; ++e) { u[e] = U[(long long)i * NU + e]; uo[e] = u[e]; }
       DevRows none;
       none.n = 0;
-      node_calc_running<NV, CHAIN>(m, none, dt0, x, u, nullptr, nullptr, xo, &c);
+      if constexpr (sizeof...(INST) == 0) node_calc_running<NV, CHAIN>(m, none, dt0, x, u, nullptr, nullptr, xo, &c);
+      else euler_node_with<NV, CHAIN>(m, inst[b]..., dt0, x, u, xo);
     }
   }
   // all reads of a block's nodes happen before its writes only within the block; a
@@ -1287,12 +1327,13 @@ AGX_UNROLL_NV
 //   k_shift / k_shift_commit; the shifted nodes are staged in LDS because node i reads node i + 1),
 //   xs[0] <- x0 (k_pin_x0) and the solver-state reset (k_reset_state).
 // Five launches of 1-10 us each otherwise: 6 % of the latency of a batch-1 step.
-template <int NV, bool CHAIN>
+template <int NV, bool CHAIN, class... INST>
 __global__ void __launch_bounds__(128) k_mpc_prologue(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                       const double *__restrict__ dts, double *__restrict__ xs,
                                                       double *__restrict__ us, double *__restrict__ x0s,
                                                       DevState *__restrict__ st, int *__restrict__ n_done, int from_pred,
-                                                      int carry, int head, int *__restrict__ head_out) {
+                                                      int carry, int head, int *__restrict__ head_out,
+                                                      const INST *__restrict__... inst) {
   constexpr int NX = 2 * NV, NU = NV, ND = NX + NU;
   extern __shared__ double sh_nodes[];  // [T][NX + NU]
   const DevModel &m = *mp;
@@ -1320,7 +1361,8 @@ AGX_UNROLL_NV
       for (int e = 0; e < NU; ++e) { u[e] = U[(long long)i * NU + e]; uo[e] = u[e]; }
       DevRows none;
       none.n = 0;
-      node_calc_running<NV, CHAIN>(m, none, dt0, x, u, nullptr, nullptr, xo, &c);
+      if constexpr (sizeof...(INST) == 0) node_calc_running<NV, CHAIN>(m, none, dt0, x, u, nullptr, nullptr, xo, &c);
+      else euler_node_with<NV, CHAIN>(m, inst[b]..., dt0, x, u, xo);
     }
     double *d = sh_nodes + (long long)i * ND;
 AGX_UNROLL_NV
@@ -1418,25 +1460,6 @@ AGX_UNROLL_NV
   }
 AGX_UNROLL_NV
   for (int e = 0; e < NX; ++e) x0[(long long)b * NX + e] = x[e];
-}
-
-// Joint accelerations of the model's kinematic tree carrying the inertials of `in`: the forward dynamics of
-// node_calc_running (world-frame bias torques and joint-space inertia, explicit inverse) with another inertial source.
-template <int NV, bool CHAIN, class INERTIALS>
-AGX_DEV void forward_dynamics_with(const DevModel &m, const INERTIALS &in, const double *x, const double *u, double *a) {
-  Kin<NV> k;
-  kinematics<NV, CHAIN>(m, x, k);
-  Dyn<NV> d;
-  double nle[NV], M[NV][NV], Minv[NV][NV];
-  bias_and_inertia<NV, CHAIN>(m, in, k, x + NV, d, nle, M);
-  spd_inverse<NV>(M, Minv);
-AGX_UNROLL_NV
-  for (int i = 0; i < NV; ++i) {
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) acc += Minv[i][j] * (u[j] - nle[j]);
-    a[i] = acc;
-  }
 }
 
 // k_feedback_rollout against a plant that is not the controller's model: instance b integrates the forward dynamics of

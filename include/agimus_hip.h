@@ -476,8 +476,8 @@ int agx_ocp_mpc_step(agx_ocp *ocp, int k0, int max_iter, int first);
 /* What consumes an MPC step: the linear feedback controller fed by
  * AgimusController.send_control_msg (agimus_controller_ros/agimus_controller.py:418-426) applies
  *   u = us[0] + K[0] (x0 - x_measured)
- * at the control rate.  Here the plant is the model (or the model with the inertials of
- * agx_ocp_set_plant_inertials): n_substeps semi-implicit Euler steps of dt_sub
+ * at the control rate.  Here the plant is the model -- instance b's own model where agx_ocp_set_model_inertials gave it
+ * one -- or the model with the inertials of agx_ocp_set_plant_inertials: n_substeps semi-implicit Euler steps of dt_sub
  * from the resident x0 under that law (+ an optional constant torque disturbance [B][nu], host);
  * the end state replaces x0, ready for agx_ocp_mpc_step(..., first = 2).           */
 int agx_ocp_feedback_rollout(agx_ocp *ocp, int n_substeps, double dt_sub, const double *disturbance);
@@ -492,6 +492,28 @@ int agx_ocp_feedback_rollout(agx_ocp *ocp, int n_substeps, double dt_sub, const 
  * queued there; the call returns once the copy is complete, so the arrays may be reused at once and every rollout queued
  * before the call has used the old plant, every later one the new.                                                    */
 int agx_ocp_set_plant_inertials(agx_ocp *ocp, const double *mass, const double *com, const double *inertia,
+                                const double *armature);
+/* The CONTROLLER's model, per instance: instance b solves its OCP on its own link inertials (one plant and many identified
+ * models, a payload the controller knows about after a grasp, a fleet of arms with individually identified parameters).
+ * Arrays, validation and ordering as agx_ocp_set_plant_inertials: host arrays at the CALLER's nv, mass [B][nv],
+ * com [B][nv][3], inertia [B][nv][9], armature [B][nv] (NULL: the model's); pad joints of a model below the capacity are
+ * massless with the padding's armature; non-finite values, a negative mass and a negative armature are refused and the
+ * handle keeps what it had; the upload runs on the solver stream after the host has waited for it.  Placements, axes,
+ * parents, gravity, frames and geometry stay the model's.  All four NULL: back to the model's own table, and from then on
+ * exactly the launches of a handle that never had per-instance inertials.
+ * READS the per-instance model -- everything that evaluates the controller's dynamics at a node of instance b: the
+ * derivative pass of every solve and MPC step (eight-lane and one-lane kernels, wide cost and constraint sets, line-search
+ * trial points included), agx_ocp_calc_diff / agx_ocp_direction / agx_ocp_qp_tiles, the re-integration of the warm-start
+ * shift (agx_ocp_shift_warmstart, agx_ocp_mpc_step) and agx_ocp_feedback_rollout when no plant is set ("instance b's model
+ * is its own plant"; a plant set with agx_ocp_set_plant_inertials still wins).
+ * STAYS on the model's own table -- functions of the handle's table, or the planner, which has the nominal robot only:
+ * agx_ocp_integrate, agx_model_rnea, agx_model_frame_*, agx_model_sensitivity, the trajectory generators and
+ * agx_traj_stream_append (reference efforts by RNEA), agx_traj_warmstart_from_reference.
+ * Scope: models of at most 7 joints after padding; a handle at the 16 / 30 / 32 capacities refuses the call.  A problem
+ * with a ControlGrav cost or constraint item refuses it too (its g(q) would be evaluated on the model's table).
+ * The call ends the tile carry of agx_ocp_mpc_step (the next step runs the full derivative pass); the carry resumes
+ * afterwards, the inertials being constant across steps.                                                              */
+int agx_ocp_set_model_inertials(agx_ocp *ocp, const double *mass, const double *com, const double *inertia,
                                 const double *armature);
 /* The resident initial state x0 [B][nx] (measured state of the next step).          */
 int agx_ocp_download_x0(agx_ocp *ocp, double *x0);
