@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "agx_traj_generic_create_weighted", "agx_traj_cartesian_sine_wi_create", "agx_traj_get_tile",
     "agx_ocp_set_plant_inertials", "agx_model_sensitivity", "agx_ocp_cost_wide", "agx_ocp_set_model_inertials",
     "agx_traj_stream_create", "agx_traj_stream_append", "agx_traj_stream_release", "agx_traj_stream_range",
-    "agx_traj_stream_joins", "agx_traj_stream_timing",
+    "agx_traj_stream_joins", "agx_traj_stream_timing", "agx_ocp_set_obstacle_placements",
 ]  # fmt: skip
 
 
@@ -595,6 +595,30 @@ class HipOcp:
     def clear_model_inertials(self):
         """Every instance solves with the model's own table again."""
         _chk(lib().agx_ocp_set_model_inertials(self._h, None, None, None, None))
+
+    # -- obstacles per instance ----------------------------------------------------
+    def set_obstacle_placements(self, frames, se3):
+        """Per-instance placements of world-fixed geometry frames (`workloads.obstacle_placements`): `frames` n ids or names of
+        the table, `se3` [B][n][12] (rotation row-major 9, then translation 3).  Instance b evaluates every collision cost and
+        constraint row that names a listed frame at se3[b][slot]; frames that are not listed keep the model's placement, a
+        listed one ignores set_geom_placement until clear_obstacle_placements.  agx_model_frame_placement / _jacobian and the
+        trajectory generators keep the model's table.  Models of at most 7 joints after padding."""
+        ids = [self.table.frame_names.index(f) if isinstance(f, str) else int(f) for f in np.asarray(frames, dtype=object).reshape(-1)]
+        n = len(ids)
+        if n < 1:
+            raise ValueError("frames: expected at least one frame (clear_obstacle_placements drops the table)")
+        a = np.asarray(se3)
+        if a.shape == (self.B, n, 3, 4) or a.shape == (self.B, n, 4, 4):
+            raise ValueError(f"se3: expected shape {(self.B, n, 12)} (rotation row-major 9, then translation 3), got the matrix form {a.shape}")
+        if a.shape != (self.B, n, 12):
+            raise ValueError(f"se3: expected shape {(self.B, n, 12)}, got {a.shape}")
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        fr = np.ascontiguousarray(ids, dtype=np.int32)
+        _chk(lib().agx_ocp_set_obstacle_placements(self._h, C.c_int(n), _p(fr), _p(a)))
+
+    def clear_obstacle_placements(self):
+        """Every instance sees the model's own placements again (the latest set_geom_placement included)."""
+        _chk(lib().agx_ocp_set_obstacle_placements(self._h, C.c_int(0), None, None))
 
     def model_sensitivity(self, x, u, dt, delta_inertia=0.01, delta_com=0.01, delta_mass=0.01):
         """[n][2 nv][10 nv] sensitivity of the Euler node's next state to the link inertials of the controller's model at the

@@ -21,7 +21,7 @@
 // launchers of the wide-cost-set kernels, compiled in a translation unit of their own (agx_cost_pairs.hip)
 extern "C" int agx_cost_pairs_launch(int dest, void *stream, long long nodes, const DevModel *m, const DevOcp *o, const DevCostWide *w,
                                      const double *dts, const double *xs, const RefView *rv, double *out, double *auxs, const DevState *st,
-                                     int phase, int sel, int which);
+                                     int phase, int sel, int which, const void *obs);
 extern "C" int agx_cost_pairs_fill_launch(void *stream, const DevCostWide *w, const double *gw_item, double *traj, long long units, int stride);
 extern "C" int agx_cost_pairs_fill_ring_launch(void *stream, const DevCostWide *w, const double *gw_item, double *traj, int B, int m_new, int end,
                                                int cap, int mirror, int stride);
@@ -166,6 +166,13 @@ struct agx_ocp {
   double *d_minert = nullptr;
   bool minert_set = false;
   std::vector<double> minert_stage;
+  // per-instance obstacle placements (agx_ocp_set_obstacle_placements, 7-joint capacity): one buffer, agx::ObstaclePlacements (the
+  // frame -> slot map) followed by se3 [B][n][12].  While set, every launch that evaluates a collision distance goes to the
+  // instantiation that reads it (launch_with_obs); unset, nothing of a launch differs from a handle that never had a table.
+  void *d_obs = nullptr;
+  size_t obs_bytes = 0;  // allocated
+  bool obs_set = false;
+  std::vector<double> obs_stage;  // host image of d_obs
   RefView rv{};
   // resident trajectory
   double *d_traj = nullptr, *d_pts = nullptr;
@@ -514,6 +521,18 @@ int ensure_canonical_tiles(agx_ocp *o) {
   return 0;
 }
 
+// A handle with per-instance obstacle placements: f(sources...) with the trailing arguments of the instantiation that reads them --
+// the obstacle table, behind the controller inertials where the kernel evaluates dynamics (running nodes) and the handle has them.
+// src_t names the template pack of such an instantiation from the arguments.
+template <class P>
+using src_t = std::remove_const_t<std::remove_pointer_t<P>>;
+template <int NV, bool READS_INERTIALS, class F>
+void launch_with_obs(agx_ocp *o, F &&f) {
+  const auto *obs = (const agx::ObstaclePlacements *)o->d_obs;
+  if constexpr (READS_INERTIALS) if (o->minert_set) { f((const agx::InstanceInertials<NV> *)o->d_minert, obs); return; }
+  f(obs);
+}
+
 int launch_calc_diff_rows(agx_ocp *o, bool masked, bool running_only) {
   if (ensure_canonical_tiles(o)) return -1;
   return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
@@ -521,6 +540,24 @@ int launch_calc_diff_rows(agx_ocp *o, bool masked, bool running_only) {
     constexpr bool CH = decltype(CHc)::value;
     const long long units = (long long)o->B * o->T;
     const int grid = (int)((units + 63) / 64);
+    if constexpr (NV <= 7) if (o->obs_set) {  // per-instance obstacle placements: both node types carry collision rows
+      const DevState *stm = masked ? o->d_state : nullptr;
+      auto both = [&](auto GENc) {
+        constexpr bool GEN = decltype(GENc)::value;
+        launch_with_obs<NV, true>(o, [&](auto... src) {
+          hipLaunchKernelGGL((agx::k_calc_diff<NV, CH, GEN, src_t<decltype(src)>...>), dim3(grid), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt,
+                             o->d_xs, o->d_us, o->rv, o->d_tiles, stm, src...);
+        });
+        if (!running_only)
+          launch_with_obs<NV, false>(o, [&](auto... src) {
+            hipLaunchKernelGGL((agx::k_calc_diff_term<NV, CH, GEN, src_t<decltype(src)>...>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model,
+                               o->d_ocp, o->d_xs, o->rv, o->d_tiles, stm, src...);
+          });
+      };
+      if (o->general) both(std::true_type()); else both(std::false_type());
+      HIPCHK(hipGetLastError());
+      return 0;
+    }
     // per-instance controller inertials: the running nodes from the instantiations that read them (terminal nodes carry costs only)
     [[maybe_unused]] const auto *inst = (const agx::InstanceInertials<NV> *)o->d_minert;
     if constexpr (NV <= 7) if (o->general) {
@@ -566,6 +603,54 @@ int launch_k1(agx_ocp *o, bool running_only, bool term_only, int phase, bool com
     // per-instance controller inertials (agx_ocp_set_model_inertials): the running nodes go to the instantiations that read
     // them; the terminal kernels evaluate costs only and are today's
     [[maybe_unused]] const auto *inst = (const agx::InstanceInertials<NV> *)o->d_minert;
+    // per-instance obstacle placements (agx_ocp_set_obstacle_placements): the instantiations that read the table, both node
+    // types.  The eight-lane kernel without a collision row evaluates no distance (a wide cost set keeps its pairs in
+    // k_cost_pairs): it stays on the launches below.
+    if constexpr (NV <= 7) if (o->obs_set) {
+      const bool lanes8 = !o->general && CH && o->k1_lanes && o->lanes_ok;
+      if (lanes8 && o->lanes_coll) {
+        const long long run_nodes = compact ? (long long)o->B * (o->T > 1 ? 2 : 1) : units;
+        const int n_run = (int)((run_nodes * 8 + 63) / 64), n_term = (int)(((long long)o->B * 8 + 63) / 64), cp = compact ? 1 : 0;
+        if (o->k1_fused && !term_only && !running_only) {
+          launch_with_obs<NV, true>(o, [&](auto... src) {
+            hipLaunchKernelGGL((agx::k_calc_qp_lj_all<NV, true, src_t<decltype(src)>...>), dim3(n_run + n_term), dim3(64), 0, o->stream, o->d_model,
+                               o->d_ocp_k1, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, n_run, phase, cp, src...);
+          });
+        } else {
+          if (!term_only)
+            launch_with_obs<NV, true>(o, [&](auto... src) {
+              hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, false, true, src_t<decltype(src)>...>), dim3(n_run), dim3(64), 0, o->stream, o->d_model,
+                                 o->d_ocp_k1, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp, src...);
+            });
+          if (!running_only)
+            launch_with_obs<NV, false>(o, [&](auto... src) {
+              hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, true, true, src_t<decltype(src)>...>), dim3(n_term), dim3(64), 0, o->stream, o->d_model,
+                                 o->d_ocp_k1, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp, src...);
+            });
+        }
+        HIPCHK(hipGetLastError());
+        return 0;
+      }
+      if (!lanes8) {  // one lane per node
+        auto both = [&](auto GENc) {
+          constexpr bool GEN = decltype(GENc)::value;
+          double *auxg = GEN ? o->d_auxg : nullptr;
+          if (!term_only)
+            launch_with_obs<NV, true>(o, [&](auto... src) {
+              hipLaunchKernelGGL((agx::k_calc_qp<NV, CH, GEN, src_t<decltype(src)>...>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream,
+                                 o->d_model, o->d_ocp, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, auxg, phase, src...);
+            });
+          if (!running_only)
+            launch_with_obs<NV, false>(o, [&](auto... src) {
+              hipLaunchKernelGGL((agx::k_calc_qp_term<NV, CH, GEN, src_t<decltype(src)>...>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model,
+                                 o->d_ocp, xs_in, o->rv, o->d_qt, o->d_aux, o->d_state, auxg, phase, src...);
+            });
+        };
+        if (o->general) both(std::true_type()); else both(std::false_type());
+        HIPCHK(hipGetLastError());
+        return 0;
+      }
+    }
     if constexpr (NV <= 7) if (o->general) {
       if (!term_only && o->minert_set)
         hipLaunchKernelGGL((agx::k_calc_qp<NV, CH, true>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
@@ -892,6 +977,19 @@ template <int NV, bool CH>
 void launch_con_eval(agx_ocp *o, const double *xs, const double *us, int phase) {
   if constexpr (NV <= 7) {
     const long long nodes = (long long)o->B * (o->T + 1);
+    if (o->obs_set) {  // per-instance obstacle placements: the same three kernels, reading the table
+      const auto *obs = (const agx::ObstaclePlacements *)o->d_obs;
+      if (o->con_wide)
+        hipLaunchKernelGGL((agx::k_con_eval_pairs<NV, agx::ObstaclePlacements>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model,
+                           o->d_ocp, xs, us, o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase, obs);
+      else if (CH && o->con_lanes)
+        hipLaunchKernelGGL((agx::k_con_eval_lj<NV, agx::ObstaclePlacements>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model,
+                           o->d_ocp, xs, us, o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase, obs);
+      else
+        hipLaunchKernelGGL((agx::k_con_eval<NV, CH, agx::ObstaclePlacements>), dim3((int)((nodes + 63) / 64)), dim3(64), 0, o->stream, o->d_model,
+                           o->d_ocp, xs, us, o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase, obs);
+      return;
+    }
     if (o->con_wide)
       hipLaunchKernelGGL((agx::k_con_eval_pairs<NV>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, xs, us,
                          o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase);
@@ -1316,7 +1414,7 @@ int launch_cost_pairs(agx_ocp *o, int dest, int sel, int phase, bool masked, int
   const DevState *st = dest == agx::kPairsToQp ? o->d_state : ((dest == agx::kPairsToCanonical && masked) ? o->d_state : nullptr);
   HIPCHK((hipError_t)agx_cost_pairs_launch(dest, (void *)o->stream, nodes, o->d_model, o->d_ocp, o->d_cw, o->d_dt, xs_in, &o->rv, out,
                                            dest == agx::kPairsToQp ? o->d_aux : nullptr, st, dest == agx::kPairsToQp ? phase : 0,
-                                           dest == agx::kPairsDistance ? 1 : sel, which));
+                                           dest == agx::kPairsDistance ? 1 : sel, which, o->obs_set ? o->d_obs : nullptr));
   return 0;
 }
 
@@ -1781,7 +1879,7 @@ void agx_ocp_destroy(agx_ocp *o) {
   if (o->copy_stream) (void)hipStreamSynchronize(o->copy_stream);
   void *ptrs[] = {o->d_mx2_elem, o->d_mx2_bnd, o->d_mx2_cl, o->d_ref_back, o->d_frames_back, o->d_snap, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us, o->d_x0, o->d_tiles, o->d_Kws, o->d_kws, o->d_Kout, o->d_dx,
                   o->d_du, o->d_ref, o->d_frames, o->d_state, o->d_ndone, o->d_scratch, o->d_traj, o->d_pts, o->d_sine, o->d_qt, o->d_aux, o->d_w, o->d_nodestat,
-                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr, o->d_plant, o->d_minert, o->d_cw};
+                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr, o->d_plant, o->d_minert, o->d_cw, o->d_obs};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (o->h_ndone) (void)hipHostFree(o->h_ndone);
@@ -2279,6 +2377,12 @@ int agx_ocp_get_residuals(agx_ocp *o, int row, double *out) {
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
     const long long units = (long long)o->B * o->T;
+    bool with_obs = false;
+    if constexpr (NV <= 7) with_obs = o->obs_set;  // the distance of a collision row at the instance's own placements
+    if constexpr (NV <= 7) if (with_obs)
+      hipLaunchKernelGGL((agx::k_residuals<NV, CH, agx::ObstaclePlacements>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
+                         o->d_xs, o->d_us, o->rv, row, o->d_scratch, (const agx::ObstaclePlacements *)o->d_obs);
+    if (!with_obs)
     hipLaunchKernelGGL((agx::k_residuals<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_xs, o->d_us, o->rv, row, o->d_scratch);
     HIPCHK(hipGetLastError());
     return 0;
@@ -2926,6 +3030,66 @@ int agx_ocp_set_model_inertials(agx_ocp *o, const double *mass, const double *co
   if (upload_inertials(o, "agx_ocp_set_model_inertials", mass, com, inertia, armature, o->minert_stage, &o->d_minert)) return -1;
   if (carry_invalidate(o)) return -1;  // every tile depends on the inertials; they are constant across steps, so the carry resumes
   o->minert_set = true;
+  return 0;
+}
+
+int agx_ocp_set_obstacle_placements(agx_ocp *o, int n_frames, const int32_t *frames, const double *se3) {
+  static const std::string fn = "agx_ocp_set_obstacle_placements";
+  if (!o) return fail(fn + ": null handle");
+  if (n_frames == 0 && !frames && !se3) {  // back to the model's placements; the buffer stays allocated for the next table
+    if (!o->obs_set) return 0;
+    if (set_device(o)) return -1;
+    if (carry_invalidate(o)) return -1;
+    o->obs_set = false;
+    return 0;
+  }
+  if (n_frames < 1 || !frames || !se3)
+    return fail(fn + ": n_frames, frames and se3 go together (0, NULL, NULL goes back to the model's placements), got n_frames = " + std::to_string(n_frames));
+  if (o->nv > 7)
+    return fail(fn + ": per-instance obstacle placements are implemented for models of at most 7 joints after padding (this handle runs at " +
+                std::to_string(o->nv) + ")");
+  // every check first: nothing of the handle changes unless all of them pass
+  int slot[AGX_MAX_FRAMES];
+  for (int f = 0; f < AGX_MAX_FRAMES; ++f) slot[f] = -1;
+  for (int s = 0; s < n_frames; ++s) {
+    const int f = frames[s];
+    const std::string at = " (entry " + std::to_string(s) + ", frame " + std::to_string(f) + ")";
+    if (f < 0 || f >= o->hm.nframes) return fail(fn + ": frame out of range" + at);
+    if (o->hm.frame_parent[f] >= 0)
+      return fail(fn + ": the frame is attached to joint " + std::to_string(o->hm.frame_parent[f]) +
+                  " and moves with the robot: its placement is relative to that joint and stays the model's" + at);
+    if (!(o->hm.frame_radius[f] > 0.0) && !(o->hm.frame_box[f][0] > 0.0 || o->hm.frame_box[f][1] > 0.0 || o->hm.frame_box[f][2] > 0.0))
+      return fail(fn + ": the frame carries no geometry" + at);
+    if (slot[f] >= 0) return fail(fn + ": frame listed twice" + at);
+    slot[f] = s;
+  }
+  const size_t B = o->B, n = (size_t)n_frames;
+  for (size_t k = 0; k < B * n * 12; ++k)
+    if (!std::isfinite(se3[k]))
+      return fail(fn + ": non-finite entry (instance " + std::to_string(k / (12 * n)) + ", frame " + std::to_string(frames[(k / 12) % n]) + ")");
+  if (set_device(o)) return -1;
+  static_assert(sizeof(agx::ObstaclePlacements) % sizeof(double) == 0, "the placements follow the header as doubles");
+  const size_t hd = sizeof(agx::ObstaclePlacements) / sizeof(double), bytes = sizeof(double) * (hd + B * n * 12);
+  // a kernel queued earlier may still read the buffer, and the copy below reads the image: the host waits for the solver's
+  // stream before it touches either, then uploads IN that stream (as upload_inertials)
+  HIPCHK(hipStreamSynchronize(o->stream));
+  if (bytes > o->obs_bytes) {
+    void *p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    if (o->d_obs) (void)hipFree(o->d_obs);
+    o->d_obs = p;
+    o->obs_bytes = bytes;
+  }
+  o->obs_stage.assign(hd + B * n * 12, 0.0);
+  agx::ObstaclePlacements head{};
+  head.n = n_frames;
+  std::memcpy(head.slot, slot, sizeof(slot));
+  std::memcpy(o->obs_stage.data(), &head, sizeof(head));
+  std::memcpy(o->obs_stage.data() + hd, se3, sizeof(double) * B * n * 12);
+  HIPCHK(hipMemcpyAsync(o->d_obs, o->obs_stage.data(), bytes, hipMemcpyHostToDevice, o->stream));
+  HIPCHK(hipStreamSynchronize(o->stream));
+  if (carry_invalidate(o)) return -1;  // the tiles of the collision rows depend on the placements; constant across steps, so the carry resumes
+  o->obs_set = true;
   return 0;
 }
 

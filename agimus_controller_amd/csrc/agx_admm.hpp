@@ -25,11 +25,14 @@ constexpr int kRhoInterval = 25;
 
 // g, collision Jacobians and the l1 violation of every node at the current (xs, us).
 // One lane per node.  cg [B][T+1][AGX_MAX_NC], cjac [B][T+1][AGX_MAX_DENSE][24] (d/dq | d/dv | d/du, 8 each).
-template <int NV, bool CHAIN>
+// OBS: empty, or ObstaclePlacements with one more argument (agx_ocp_set_obstacle_placements): the collision rows of instance b
+// then place the listed world-fixed geometry at the instance's own pose.
+template <int NV, bool CHAIN, class... OBS>
 __global__ void __launch_bounds__(64) k_con_eval(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                  const double *__restrict__ xs, const double *__restrict__ us,
                                                  double *__restrict__ cg, double *__restrict__ cjac,
-                                                 double *__restrict__ nodestat, const DevState *__restrict__ st, int phase) {
+                                                 double *__restrict__ nodestat, const DevState *__restrict__ st, int phase,
+                                                 const OBS *__restrict__... obs) {
   constexpr int NX = 2 * NV, NU = NV;
   const DevModel &m = *mp;
   const DevOcp &o = *op;
@@ -45,7 +48,7 @@ __global__ void __launch_bounds__(64) k_con_eval(const DevModel *__restrict__ mp
 #pragma unroll
   for (int i = 0; i < NU; ++i) u[i] = (t < T) ? us[((long long)b * T + t) * NU + i] : 0.0;
   for (int k = 0; k < AGX_MAX_NC; ++k) g[k] = 0.0;
-  constraints_eval<NV, CHAIN, true>(m, c, x, u, g, cj);
+  constraints_eval<NV, CHAIN, true>(m, c, x, u, g, cj, world_of(b, obs...));
   for (int k = 0; k < c.nc; ++k) cg[node * AGX_MAX_NC + k] = g[k];
   for (int r = 0; r < c.ncoll; ++r)
     for (int j = 0; j < 24; ++j) cjac[(node * AGX_MAX_DENSE + r) * 24 + j] = ((j & 7) < NV) ? cj[r][j] : 0.0;

@@ -6,11 +6,23 @@
 
 extern "C" {
 
-// k_cost_pairs<7, dest> on a grid of 8 lanes per node; returns the hipError_t of the launch
+// k_cost_pairs<7, dest> on a grid of 8 lanes per node; returns the hipError_t of the launch.  obs: null, or the device table of
+// agx_ocp_set_obstacle_placements (agx::ObstaclePlacements): the instantiations that read it
 int agx_cost_pairs_launch(int dest, void *stream, long long nodes, const DevModel *m, const DevOcp *o, const DevCostWide *w, const double *dts,
-                          const double *xs, const RefView *rv, double *out, double *auxs, const DevState *st, int phase, int sel, int which) {
+                          const double *xs, const RefView *rv, double *out, double *auxs, const DevState *st, int phase, int sel, int which,
+                          const void *obs) {
   const dim3 grid((unsigned)((nodes * 8 + 63) / 64)), blk(64);
   hipStream_t s = (hipStream_t)stream;
+  if (obs) {
+    const auto *ob = (const agx::ObstaclePlacements *)obs;
+    if (dest == agx::kPairsToQp)
+      hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsToQp>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which, ob);
+    else if (dest == agx::kPairsToCanonical)
+      hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsToCanonical>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which, ob);
+    else
+      hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsDistance>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which, ob);
+    return (int)hipGetLastError();
+  }
   if (dest == agx::kPairsToQp)
     hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsToQp>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which);
   else if (dest == agx::kPairsToCanonical)

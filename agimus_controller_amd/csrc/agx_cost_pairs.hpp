@@ -28,12 +28,14 @@ namespace agx {
 // DEST kPairsToCanonical: into Lx[q], Lxx[qq] and cost of the canonical tile (agx_ocp_calc_diff); `st` may be null.
 // DEST kPairsDistance: the distance of pair `which` at the running nodes, out [B][T] (agx_ocp_get_residuals).
 // sel: 0 every node, 1 running nodes, 2 terminal nodes.
-template <int NV, int DEST>
+// OBS: empty, or ObstaclePlacements with one more argument (agx_ocp_set_obstacle_placements): a world-fixed geometry listed in
+// the table is placed at the pose of the node's instance, a per-lane load in place of the model's entry.
+template <int NV, int DEST, class... OBS>
 __global__ void __launch_bounds__(64) k_cost_pairs(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                    const DevCostWide *__restrict__ wp, const double *__restrict__ dts,
                                                    const double *__restrict__ xs, RefView rv, double *__restrict__ out,
                                                    double *__restrict__ auxs, const DevState *__restrict__ st, int phase, int sel,
-                                                   int which) {
+                                                   int which, const OBS *__restrict__... obs) {
   constexpr int NX = 2 * NV, NH = NV * (NV + 1) / 2;
   static_assert(NV <= 7, "8 lanes per node: one lane per joint, lane 7 carries the padding column");
   __shared__ double s_mod[8][16];     // placement 12 | axis 3 of every joint
@@ -131,10 +133,11 @@ __global__ void __launch_bounds__(64) k_cost_pairs(const DevModel *__restrict__ 
         mv3(Rp, fpl + 9, tt);
         pg[gi][0] = pp[0] + tt[0]; pg[gi][1] = pp[1] + tt[1]; pg[gi][2] = pp[2] + tt[2];
       } else {
+        const double *wpl = world_of(b, obs...).world(fpl, fr[gi]);
 #pragma unroll
-        for (int e = 0; e < 9; ++e) Rg[gi][e] = fpl[e];
+        for (int e = 0; e < 9; ++e) Rg[gi][e] = wpl[e];
 #pragma unroll
-        for (int e = 0; e < 3; ++e) pg[gi][e] = fpl[9 + e];
+        for (int e = 0; e < 3; ++e) pg[gi][e] = wpl[9 + e];
       }
     }
     double ca[3], cb[3], nn[3];

@@ -23,6 +23,8 @@
 #endif
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/agimus_hip.h"
 
 #define AGX_MAX_FRAMES 72
@@ -813,9 +815,50 @@ AGX_DEV void log6(const double *R, const double *p, double *r, double *TL, doubl
   }
 }
 
-// world placement of an operational frame
-template <int NV>
-AGX_DEV void frame_world(const DevModel &m, const Kin<NV> &k, int frame, double *R, double *p, int *joint) {
+// ------------------------------------------------------------------ obstacle placements per instance
+// agx_ocp_set_obstacle_placements gives every instance its own placement of the listed WORLD-FIXED geometry frames (frame_parent
+// < 0: the host refuses any other frame).  One device buffer: this header, then se3 [B][n][12] in the layout of
+// DevModel::frame_placement.  slot[f] is the column of frame f, or -1 for a frame that keeps the model's placement.
+struct ObstaclePlacements {
+  int n, pad;
+  int slot[AGX_MAX_FRAMES];
+  AGX_DEV const double *se3() const { return reinterpret_cast<const double *>(this + 1); }
+};
+// Where a collision site takes the placement of a world-fixed geometry frame from.  ModelWorld: the model's table, the pointer it
+// is given, untouched -- every kernel of a handle without a table.  InstanceWorld: the table of instance b for a listed frame
+// (per-lane loads: the lanes of a wave belong to several instances), the model's for the others.
+struct ModelWorld {
+  AGX_DEV const double *world(const double *model_pl, int) const { return model_pl; }
+};
+struct InstanceWorld {
+  const ObstaclePlacements *obs;
+  int b;
+  AGX_DEV const double *world(const double *model_pl, int frame) const {
+    const int s = obs->slot[frame];
+    return s >= 0 ? obs->se3() + ((long long)b * obs->n + s) * 12 : model_pl;
+  }
+};
+// Kernels take their per-instance sources through a trailing template pack: empty (the kernel on the model's tables, argument
+// for argument), InstanceInertials<NV> (agx_ocp_set_model_inertials), ObstaclePlacements, or both in that order.
+template <class T, class... A>
+constexpr bool pack_has = (std::is_same<T, A>::value || ...);
+template <class T>
+AGX_DEV const T *pack_ptr() { return nullptr; }
+template <class T, class A0, class... A>
+AGX_DEV const T *pack_ptr(const A0 *a0, const A *... rest) {
+  if constexpr (std::is_same<T, A0>::value) return a0;
+  else return pack_ptr<T>(rest...);
+}
+// the placement source of instance b for a kernel with the pack `src`
+template <class... A>
+AGX_DEV auto world_of(int b, const A *... src) {
+  if constexpr (pack_has<ObstaclePlacements, A...>) return InstanceWorld{pack_ptr<ObstaclePlacements>(src...), b};
+  else return ModelWorld{};
+}
+
+// world placement of an operational frame; W: the source of a world-fixed frame's placement (the collision sites pass theirs)
+template <int NV, class W = ModelWorld>
+AGX_DEV void frame_world(const DevModel &m, const Kin<NV> &k, int frame, double *R, double *p, int *joint, const W &w = W()) {
   const int par = m.frame_parent[frame];
   *joint = par;
   if (par >= 0) {
@@ -838,10 +881,11 @@ AGX_UNROLL_NV
     mv3(Rp, &m.frame_placement[frame][9], t);
     p[0] = pp[0] + t[0]; p[1] = pp[1] + t[1]; p[2] = pp[2] + t[2];
   } else {
+    const double *fpl = w.world(m.frame_placement[frame], frame);
 #pragma unroll
-    for (int e = 0; e < 9; ++e) R[e] = m.frame_placement[frame][e];
+    for (int e = 0; e < 9; ++e) R[e] = fpl[e];
 #pragma unroll
-    for (int e = 0; e < 3; ++e) p[e] = m.frame_placement[frame][9 + e];
+    for (int e = 0; e < 3; ++e) p[e] = fpl[9 + e];
   }
 }
 
@@ -1020,12 +1064,12 @@ AGX_DEV double collision_distance_placed(const DevModel &m, int fa, int fb, cons
   for (int e = 0; e < 3; ++e) n[e] *= inv;
   return sgn * dn - (m.frame_radius[fa] + m.frame_radius[fb]);
 }
-template <int NV>
+template <int NV, class W = ModelWorld>
 AGX_DEV double collision_distance(const DevModel &m, const Kin<NV> &k, int fa, int fb, double *ca, double *cb, double *n,
-                                  int *ja, int *jb) {
+                                  int *ja, int *jb, const W &w = W()) {
   double Ra[9], pa[3], Rb[9], pb[3];
-  frame_world<NV>(m, k, fa, Ra, pa, ja);
-  frame_world<NV>(m, k, fb, Rb, pb, jb);
+  frame_world<NV>(m, k, fa, Ra, pa, ja, w);
+  frame_world<NV>(m, k, fb, Rb, pb, jb, w);
   return collision_distance_placed(m, fa, fb, Ra, pa, Rb, pb, ca, cb, n);
 }
 
@@ -1038,9 +1082,10 @@ struct CostAcc {
 };
 
 // Evaluates the cost rows of one node.  DIFF = false: value only (line search).
-template <int NV, bool CHAIN, bool TERM, bool DIFF>
+// W: where the collision rows take the placement of a world-fixed geometry from (ModelWorld / InstanceWorld above).
+template <int NV, bool CHAIN, bool TERM, bool DIFF, class W = ModelWorld>
 AGX_DEV void node_costs(const DevModel &m, const DevRows &rows, const Kin<NV> &k, const double *x, const double *u,
-                        const double *ref, const int *frames, CostAcc<NV> &c) {
+                        const double *ref, const int *frames, CostAcc<NV> &c, const W &w = W()) {
   c.cost = 0.0;
   if (DIFF) {
 AGX_UNROLL_NV
@@ -1240,7 +1285,7 @@ AGX_UNROLL_NV
       // colmpc.ResidualDistanceCollision (ocp_croco_generic.py:524-533) with a scalar activation
       double ca[3], cb[3], n[3];
       int ja, jb;
-      const double d = collision_distance<NV>(m, k, rows.frame[r], rows.frame_b[r], ca, cb, n, &ja, &jb);
+      const double d = collision_distance<NV>(m, k, rows.frame[r], rows.frame_b[r], ca, cb, n, &ja, &jb, w);
       double a, ar, arr;
       activation1(rows.act[r], rows.alpha[r], aw[0], d, a, ar, arr);
       c.cost += wi * a;
@@ -1283,9 +1328,9 @@ namespace agx {
 // Constraints of one node (ConstraintModelManager of the node's differential model): g stacked over
 // the rows; JAC also returns the Jacobian rows [d/dq (8) | d/dv (8) | d/du (8)] of every component of
 // the rows with dense Jacobians (slot coll_slot[r] + e); State / Control rows have identity Jacobians.
-template <int NV, bool CHAIN, bool JAC>
+template <int NV, bool CHAIN, bool JAC, class W = ModelWorld>
 AGX_DEV void constraints_eval(const DevModel &m, const DevCons &c, const double *x, const double *u, double *g,
-                              double (*cj)[24]) {
+                              double (*cj)[24], const W &w = W()) {
   Kin<NV> k;
   if (c.ncoll > 0) kinematics<NV, CHAIN>(m, x, k);
   if (JAC)
@@ -1385,7 +1430,7 @@ AGX_UNROLL_NV
     } else if (kind == AGX_RES_COLLISION) {
       double ca[3], cb[3], n[3];
       int ja, jb;
-      g[off] = collision_distance<NV>(m, k, c.frame[r], c.frame_b[r], ca, cb, n, &ja, &jb);
+      g[off] = collision_distance<NV>(m, k, c.frame[r], c.frame_b[r], ca, cb, n, &ja, &jb, w);
       if (JAC) {
         double *gj = cj[c.coll_slot[r]];
 AGX_UNROLL_NV

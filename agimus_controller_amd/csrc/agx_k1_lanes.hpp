@@ -117,14 +117,20 @@ struct LjModel {
 // come from lmod.  The loads sit right in front of their only uses (the world-frame body inertia; the armature on the diagonal
 // of M), after the cost phase, so that they add nothing to the long live ranges.  Only running nodes read inertials: a terminal
 // node carries costs alone (Ib, Ic and m6 below are dead under TERM), so the callers never set PINST together with TERM.
-template <int NV, bool TERM, bool COLL = false, bool PINST = false>
+// POBS (with COLL): the two geometry placements the prologue stages in frm[2] / frm[3] come from the table of the node's
+// instance for a frame listed in obs (agx_ocp_set_obstacle_placements; listed frames are world-fixed, so only the branch that
+// copies the placement as it is ever sees them).  Lane l8 of the node loads its share of the 12 doubles, as it does from the
+// model; the cost phase reads LDS as before.  Terminal nodes carry collision rows: POBS goes with TERM.
+template <int NV, bool TERM, bool COLL = false, bool PINST = false, bool POBS = false>
 __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds, LjModel &lmod, const DevModel *__restrict__ mp,
                                                 const DevOcp *__restrict__ op, const double *__restrict__ dts,
                                                 const double *__restrict__ xs, const double *__restrict__ us, const RefView &rv,
                                                 double *__restrict__ qts, double *__restrict__ auxs,
                                                 const DevState *__restrict__ st, const int phase, const int compact,
-                                                const InstanceInertials<NV> *__restrict__ inst = nullptr) {
+                                                const InstanceInertials<NV> *__restrict__ inst = nullptr,
+                                                const ObstaclePlacements *__restrict__ obs = nullptr) {
   static_assert(!(PINST && TERM), "terminal nodes read no inertials");
+  static_assert(COLL || !POBS, "only the collision row reads obstacle placements");
   constexpr int NX = 2 * NV;
   typedef QT<NV> Q;
   typedef AUX<NV> A;
@@ -189,6 +195,11 @@ __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds
     if constexpr (COLL) {
       for (int r = 0; r < rows.n; ++r) {
         if (rows.kind[r] != AGX_RES_COLLISION) continue;
+        if constexpr (POBS) {
+          const InstanceWorld w{obs, b};
+          const double *fa = w.world(m.frame_placement[rows.frame[r]], rows.frame[r]), *fb = w.world(m.frame_placement[rows.frame_b[r]], rows.frame_b[r]);
+          for (int e = l8; e < 12; e += 8) { L.u.c.frm[2][e] = fa[e]; L.u.c.frm[3][e] = fb[e]; }
+        } else
         for (int e = l8; e < 12; e += 8) { L.u.c.frm[2][e] = m.frame_placement[rows.frame[r]][e]; L.u.c.frm[3][e] = m.frame_placement[rows.frame_b[r]][e]; }
         if (l8 == 0) { L.cpar[0] = m.frame_parent[rows.frame[r]]; L.cpar[1] = m.frame_parent[rows.frame_b[r]]; L.cpar[2] = r; }
         break;
@@ -707,18 +718,20 @@ __device__ __forceinline__ void calc_qp_lj_body(const long long blk, LjNode *lds
 }
 
 // Separate launches (timing, terminal-only / running-only callers)
-// INST: empty, or InstanceInertials<NV> with one more argument, the per-instance controller model (PINST of the body) -- the
-// kernel with the pack empty is today's, argument for argument.
+// INST: empty, InstanceInertials<NV> (the per-instance controller model, PINST of the body), ObstaclePlacements (POBS) or both
+// in that order, one more argument each -- the kernel with the pack empty is today's, argument for argument.
 template <int NV, bool TERM, bool COLL = false, class... INST>
 __global__ void __launch_bounds__(64, AGX_K1_WAVES) k_calc_qp_lj(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                     const double *__restrict__ dts, const double *__restrict__ xs,
                                                     const double *__restrict__ us, RefView rv, double *__restrict__ qts,
                                                     double *__restrict__ auxs, const DevState *__restrict__ st, int phase, int compact,
                                                     const INST *__restrict__... inst) {
-  static_assert(!(TERM && sizeof...(INST) > 0), "terminal nodes read no inertials: launch the kernel without them");
+  static_assert(!(TERM && pack_has<InstanceInertials<NV>, INST...>), "terminal nodes read no inertials: launch the kernel without them");
   __shared__ LjNode lds[8];  // one wave per workgroup: 8 nodes
   __shared__ LjModel lmod;
-  calc_qp_lj_body<NV, TERM, COLL, (sizeof...(INST) > 0)>(blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact, inst...);
+  calc_qp_lj_body<NV, TERM, COLL, pack_has<InstanceInertials<NV>, INST...>, pack_has<ObstaclePlacements, INST...>>(
+      blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact, pack_ptr<InstanceInertials<NV>>(inst...),
+      pack_ptr<ObstaclePlacements>(inst...));
 }
 
 // The derivative pass of one SQP iteration in ONE launch: the first n_run workgroups take the running
@@ -733,9 +746,12 @@ __global__ void __launch_bounds__(64, AGX_K1_WAVES) k_calc_qp_lj_all(const DevMo
   __shared__ LjNode lds[8];
   __shared__ LjModel lmod;
   if ((int)blockIdx.x < n_run)
-    calc_qp_lj_body<NV, false, COLL, (sizeof...(INST) > 0)>(blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact, inst...);
+    calc_qp_lj_body<NV, false, COLL, pack_has<InstanceInertials<NV>, INST...>, pack_has<ObstaclePlacements, INST...>>(
+        blockIdx.x, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact, pack_ptr<InstanceInertials<NV>>(inst...),
+        pack_ptr<ObstaclePlacements>(inst...));
   else
-    calc_qp_lj_body<NV, true, COLL>((long long)blockIdx.x - n_run, lds, lmod, mp, op, dts, xs, us, rv, qts, auxs, st, phase, compact);
+    calc_qp_lj_body<NV, true, COLL, false, pack_has<ObstaclePlacements, INST...>>((long long)blockIdx.x - n_run, lds, lmod, mp, op, dts, xs, us, rv, qts,
+                                                                                 auxs, st, phase, compact, nullptr, pack_ptr<ObstaclePlacements>(inst...));
 }
 
 // Constraint values, Jacobian rows and the l1 violation of every node (k_con_eval, agx_admm.hpp) with 8 lanes per node for the
@@ -744,11 +760,14 @@ __global__ void __launch_bounds__(64, AGX_K1_WAVES) k_calc_qp_lj_all(const DevMo
 // redundantly by the 8 lanes, lane j writes its column of the distance gradient.  The one-lane kernel (512 VGPRs, private
 // arrays) took 90 us per launch at B = 256, T = 200; problems with other constraint kinds still use it.
 // cg [B][T+1][AGX_MAX_NC], cjac [B][T+1][AGX_MAX_DENSE][24] (d/dq | d/dv | d/du, 8 each).
-template <int NV>
+// OBS: empty, or ObstaclePlacements with one more argument: a world-fixed geometry listed in the table is placed at the pose of
+// the node's instance (a per-lane load: the eight nodes of a wave can belong to several instances).
+template <int NV, class... OBS>
 __global__ void __launch_bounds__(64) k_con_eval_lj(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                     const double *__restrict__ xs, const double *__restrict__ us,
                                                     double *__restrict__ cg, double *__restrict__ cjac,
-                                                    double *__restrict__ nodestat, const DevState *__restrict__ st, int phase) {
+                                                    double *__restrict__ nodestat, const DevState *__restrict__ st, int phase,
+                                                    const OBS *__restrict__... obs) {
   constexpr int NX = 2 * NV;
   __shared__ double s_mod[8][16];  // placement 12 | axis 3 of every joint
   const DevModel &m = *mp;
@@ -848,10 +867,11 @@ __global__ void __launch_bounds__(64) k_con_eval_lj(const DevModel *__restrict__
           mv3(Rp, fpl + 9, tt);
           pg[gi][0] = pp[0] + tt[0]; pg[gi][1] = pp[1] + tt[1]; pg[gi][2] = pp[2] + tt[2];
         } else {
+          const double *wpl = world_of(b, obs...).world(fpl, frame);
 #pragma unroll
-          for (int e = 0; e < 9; ++e) Rg[gi][e] = fpl[e];
+          for (int e = 0; e < 9; ++e) Rg[gi][e] = wpl[e];
 #pragma unroll
-          for (int e = 0; e < 3; ++e) pg[gi][e] = fpl[9 + e];
+          for (int e = 0; e < 3; ++e) pg[gi][e] = wpl[9 + e];
         }
       }
       double ca[3], cb[3], nn[3];
@@ -882,11 +902,13 @@ __global__ void __launch_bounds__(64) k_con_eval_lj(const DevModel *__restrict__
 // and their whole gradient row in q from the staged joints (serial chain: joints up to a frame's parent move it; a self-collision
 // pair gets the terms of both frames).  State / Control rows as in k_con_eval_lj.
 // cg [B][T+1][cstride], cjac [B][T+1][jstride][8] (d/dq: a distance depends on q alone).
-template <int NV>
+// OBS: as k_con_eval_lj.
+template <int NV, class... OBS>
 __global__ void __launch_bounds__(64) k_con_eval_pairs(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                        const double *__restrict__ xs, const double *__restrict__ us,
                                                        double *__restrict__ cg, double *__restrict__ cjac,
-                                                       double *__restrict__ nodestat, const DevState *__restrict__ st, int phase) {
+                                                       double *__restrict__ nodestat, const DevState *__restrict__ st, int phase,
+                                                       const OBS *__restrict__... obs) {
   constexpr int NX = 2 * NV;
   __shared__ double s_mod[8][16];     // placement 12 | axis 3 of every joint
   __shared__ double s_kin[8][8][16];  // [node of the block][joint]: world rotation 9 | origin 3 | axis 3
@@ -993,10 +1015,11 @@ __global__ void __launch_bounds__(64) k_con_eval_pairs(const DevModel *__restric
         mv3(Rp, fpl + 9, tt);
         pg[gi][0] = pp[0] + tt[0]; pg[gi][1] = pp[1] + tt[1]; pg[gi][2] = pp[2] + tt[2];
       } else {
+        const double *wpl = world_of(b, obs...).world(fpl, fr[gi]);
 #pragma unroll
-        for (int e = 0; e < 9; ++e) Rg[gi][e] = fpl[e];
+        for (int e = 0; e < 9; ++e) Rg[gi][e] = wpl[e];
 #pragma unroll
-        for (int e = 0; e < 3; ++e) pg[gi][e] = fpl[9 + e];
+        for (int e = 0; e < 3; ++e) pg[gi][e] = wpl[9 + e];
       }
     }
     double ca[3], cb[3], nn[3];

@@ -33,10 +33,12 @@ __device__ __forceinline__ void count_carriable(DevState &S, int *n_done) {
 // ---------------------------------------------------------------------------
 // K1: derivative pass over the running nodes.  unit = b*T + t, one lane each.
 // ---------------------------------------------------------------------------
-// INST (here and in the other one-lane kernels): empty, or InstanceInertials<NV> with one more argument, the per-instance
-// inertials of the controller's model (agx_ocp_set_model_inertials): instance b then takes mass, centre of mass, inertia and
-// armature of every link from inst[b] through the source overloads of agx_device.hpp.  With the pack empty the kernel is,
-// argument for argument and line for line, the one on the model's own table.
+// INST (here and in the other one-lane kernels): the per-instance sources of the kernel, one more argument each.
+// InstanceInertials<NV>: the inertials of the controller's model (agx_ocp_set_model_inertials): instance b then takes mass, centre
+// of mass, inertia and armature of every link from inst[b] through the source overloads of agx_device.hpp.
+// ObstaclePlacements (after the inertials, where both are given): the per-instance placements of world-fixed geometry
+// (agx_ocp_set_obstacle_placements), read by the collision rows through world_of(b, inst...).  With the pack empty the kernel
+// is, argument for argument and line for line, the one on the model's own tables.
 template <int NV, bool CHAIN, bool GEN = false, class... INST>
 __global__ void __launch_bounds__(64) k_calc_diff(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                   const double *__restrict__ dts, const double *__restrict__ xs,
@@ -66,8 +68,8 @@ __global__ void __launch_bounds__(64) k_calc_diff(const DevModel *__restrict__ m
   kinematics<NV, CHAIN>(m, x, k);
   Dyn<NV> d;
   double nle[NV], M[NV][NV], Minv[NV][NV], qdd[NV];
-  if constexpr (sizeof...(INST) == 0) bias_and_inertia<NV, CHAIN>(m, k, x + NV, d, nle, M);
-  else bias_and_inertia<NV, CHAIN>(m, inst[b]..., k, x + NV, d, nle, M);
+  if constexpr (!pack_has<InstanceInertials<NV>, INST...>) bias_and_inertia<NV, CHAIN>(m, k, x + NV, d, nle, M);
+  else bias_and_inertia<NV, CHAIN>(m, pack_ptr<InstanceInertials<NV>>(inst...)[b], k, x + NV, d, nle, M);
   spd_inverse<NV>(M, Minv);
 AGX_UNROLL_NV
   for (int i = 0; i < NV; ++i) {
@@ -111,7 +113,7 @@ AGX_UNROLL_NV
     }
   }
   CostAcc<NV> c;
-  node_costs<NV, CHAIN, false, true>(m, o.rows[0], k, x, u, ref_at(rv, b, t, T), frames_at(rv, b, t, T), c);
+  node_costs<NV, CHAIN, false, true>(m, o.rows[0], k, x, u, ref_at(rv, b, t, T), frames_at(rv, b, t, T), c, world_of(b, inst...));
   CostGen<NV> g;
   if constexpr (GEN) node_costs_general<NV, CHAIN, false, true>(m, o.rows[0], k, x, u, ref_at(rv, b, t, T), frames_at(rv, b, t, T), c, g);
   tile[TO::cost] = dt * c.cost;
@@ -135,10 +137,12 @@ AGX_UNROLL_NV
 }
 
 // terminal nodes: cost only, xnext = x (dt = 0, cost not scaled)
-template <int NV, bool CHAIN, bool GEN = false>
+// OBS: empty, or ObstaclePlacements with one more argument (terminal nodes carry collision rows, and no dynamics)
+template <int NV, bool CHAIN, bool GEN = false, class... OBS>
 __global__ void __launch_bounds__(64) k_calc_diff_term(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                        const double *__restrict__ xs, RefView rv,
-                                                       double *__restrict__ tiles, const DevState *__restrict__ st) {
+                                                       double *__restrict__ tiles, const DevState *__restrict__ st,
+                                                       const OBS *__restrict__... obs) {
   constexpr int NX = 2 * NV, NU = NV;
   typedef TileOff<NV> TO;
   const DevModel &m = *mp;
@@ -155,7 +159,7 @@ __global__ void __launch_bounds__(64) k_calc_diff_term(const DevModel *__restric
   Kin<NV> k;
   kinematics<NV, CHAIN>(m, x, k);
   CostAcc<NV> c;
-  node_costs<NV, CHAIN, true, true>(m, o.rows[1], k, x, nullptr, ref_at(rv, b, T, T), frames_at(rv, b, T, T), c);
+  node_costs<NV, CHAIN, true, true>(m, o.rows[1], k, x, nullptr, ref_at(rv, b, T, T), frames_at(rv, b, T, T), c, world_of(b, obs...));
   CostGen<NV> g;
   if constexpr (GEN) node_costs_general<NV, CHAIN, true, true>(m, o.rows[1], k, x, nullptr, ref_at(rv, b, T, T), frames_at(rv, b, T, T), c, g);
   tile[TO::cost] = c.cost;
@@ -234,8 +238,8 @@ __device__ __forceinline__ void calc_qp_body(const long long unit, const DevMode
   kinematics<NV, CHAIN>(m, x, k);
   Dyn<NV> d;
   double nle[NV], M[NV][NV], L[NV][NV], Minv[NV][NV], qdd[NV];
-  if constexpr (sizeof...(INST) == 0) bias_and_inertia<NV, CHAIN>(m, k, x + NV, d, nle, M);
-  else bias_and_inertia<NV, CHAIN>(m, inst[b]..., k, x + NV, d, nle, M);
+  if constexpr (!pack_has<InstanceInertials<NV>, INST...>) bias_and_inertia<NV, CHAIN>(m, k, x + NV, d, nle, M);
+  else bias_and_inertia<NV, CHAIN>(m, pack_ptr<InstanceInertials<NV>>(inst...)[b], k, x + NV, d, nle, M);
 AGX_UNROLL_NV
   for (int i = 0; i < NV; ++i)
 #pragma unroll
@@ -260,7 +264,7 @@ AGX_UNROLL_NV
   double tq[NV][NV], tv[NV][NV];
   rnea_derivatives<NV, CHAIN>(m, k, d, x + NV, qdd, tq, tv);
   CostAcc<NV> c;
-  node_costs<NV, CHAIN, false, true>(m, o.rows[0], k, x, u, ref_at(rv, b, t, T), frames_at(rv, b, t, T), c);
+  node_costs<NV, CHAIN, false, true>(m, o.rows[0], k, x, u, ref_at(rv, b, t, T), frames_at(rv, b, t, T), c, world_of(b, inst...));
   CostGen<NV> g;
   if constexpr (GEN) node_costs_general<NV, CHAIN, false, true>(m, o.rows[0], k, x, u, ref_at(rv, b, t, T), frames_at(rv, b, t, T), c, g);
   qt[Q::cost] = dt * c.cost;
@@ -342,11 +346,11 @@ __global__ void __launch_bounds__(64) k_calc_qp(const DevModel *__restrict__ mp,
   calc_qp_body<NV, CHAIN, GEN>((long long)blockIdx.x * blockDim.x + threadIdx.x, mp, op, dts, xs, us, rv, qts, auxs, st, auxg, phase, inst...);
 }
 
-template <int NV, bool CHAIN, bool GEN = false>
+template <int NV, bool CHAIN, bool GEN = false, class... OBS>
 __device__ __forceinline__ void calc_qp_term_body(const int b, const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                   const double *__restrict__ xs, const RefView &rv, double *__restrict__ qts,
                                                   double *__restrict__ auxs, const DevState *__restrict__ st,
-                                                  double *__restrict__ auxg = nullptr, int phase = 0) {
+                                                  double *__restrict__ auxg = nullptr, int phase = 0, const OBS *__restrict__... obs) {
   constexpr int NX = 2 * NV;
   typedef QT<NV> Q;
   typedef AUX<NV> A;
@@ -364,7 +368,7 @@ __device__ __forceinline__ void calc_qp_term_body(const int b, const DevModel *_
   Kin<NV> k;
   kinematics<NV, CHAIN>(m, x, k);
   CostAcc<NV> c;
-  node_costs<NV, CHAIN, true, true>(m, o.rows[1], k, x, nullptr, ref_at(rv, b, T, T), frames_at(rv, b, T, T), c);
+  node_costs<NV, CHAIN, true, true>(m, o.rows[1], k, x, nullptr, ref_at(rv, b, T, T), frames_at(rv, b, T, T), c, world_of(b, obs...));
   CostGen<NV> g;
   if constexpr (GEN) node_costs_general<NV, CHAIN, true, true>(m, o.rows[1], k, x, nullptr, ref_at(rv, b, T, T), frames_at(rv, b, T, T), c, g);
   qt[Q::cost] = c.cost;
@@ -400,12 +404,12 @@ AGX_UNROLL_NV
   }
 }
 
-template <int NV, bool CHAIN, bool GEN = false>
+template <int NV, bool CHAIN, bool GEN = false, class... OBS>
 __global__ void __launch_bounds__(64) k_calc_qp_term(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op,
                                                      const double *__restrict__ xs, RefView rv, double *__restrict__ qts,
                                                      double *__restrict__ auxs, const DevState *__restrict__ st,
-                                                     double *__restrict__ auxg = nullptr, int phase = 0) {
-  calc_qp_term_body<NV, CHAIN, GEN>(blockIdx.x * blockDim.x + threadIdx.x, mp, op, xs, rv, qts, auxs, st, auxg, phase);
+                                                     double *__restrict__ auxg = nullptr, int phase = 0, const OBS *__restrict__... obs) {
+  calc_qp_term_body<NV, CHAIN, GEN>(blockIdx.x * blockDim.x + threadIdx.x, mp, op, xs, rv, qts, auxs, st, auxg, phase, obs...);
 }
 
 __device__ __forceinline__ double wave_max(double v) {
@@ -1815,9 +1819,11 @@ AGX_UNROLL_NV
 
 // residual vector of one running row at the resident solution (debug data,
 // ocp_croco_generic.py:840-853): out [B][T][nr]
-template <int NV, bool CHAIN>
+// OBS: empty, or ObstaclePlacements with one more argument (the distance of a collision row at the instance's own placements)
+template <int NV, bool CHAIN, class... OBS>
 __global__ void k_residuals(const DevModel *__restrict__ mp, const DevOcp *__restrict__ op, const double *__restrict__ xs,
-                            const double *__restrict__ us, RefView rv, int row, double *__restrict__ out) {
+                            const double *__restrict__ us, RefView rv, int row, double *__restrict__ out,
+                            const OBS *__restrict__... obs) {
   constexpr int NX = 2 * NV, NU = NV;
   const DevModel &m = *mp;
   const DevOcp &o = *op;
@@ -1869,7 +1875,7 @@ __global__ void k_residuals(const DevModel *__restrict__ mp, const DevOcp *__res
     kinematics<NV, CHAIN>(m, ql, k);
     double ca[3], cb[3], n[3];
     int ja, jb;
-    dst[0] = collision_distance<NV>(m, k, rows.frame[row], rows.frame_b[row], ca, cb, n, &ja, &jb);
+    dst[0] = collision_distance<NV>(m, k, rows.frame[row], rows.frame_b[row], ca, cb, n, &ja, &jb, world_of(b, obs...));
   } else if (kind == AGX_RES_FRAME_VELOCITY) {
     double xl[NX];
     for (int e = 0; e < NX; ++e) xl[e] = x[e];

@@ -388,6 +388,46 @@ def stack_inertials(tables):
             np.stack([np.asarray(t.armature, dtype=float).reshape(nv) for t in tables]))
 
 
+def obstacle_placements(table, frames, B: int, seed: int, max_shift: float = 0.1, max_angle: float = 0.5):
+    """se3 [B][n][12] for `HipOcp.set_obstacle_placements`: seeded placements of the frames `frames` (ids or names) around the
+    table's own.  Instance 0 keeps the table's placements; every other instance and frame is translated by a seeded vector of
+    length at most max_shift and rotated (about the frame's own origin, in the world) by a seeded angle within +-max_angle about
+    a seeded axis."""
+    ids = [table.frame_id(f) for f in frames]
+    base = np.asarray(table.frame_placement, dtype=float).reshape(-1, 12)[ids]
+    out = np.broadcast_to(base, (B, len(ids), 12)).copy()
+    for b in range(1, B):
+        for s in range(len(ids)):
+            rng = np.random.default_rng([seed, b, s])
+            d = rng.normal(size=3)
+            d *= max_shift * rng.uniform() ** (1.0 / 3.0) / np.linalg.norm(d)
+            ax = rng.normal(size=3)
+            ax /= np.linalg.norm(ax)
+            ang = rng.uniform(-max_angle, max_angle)
+            K = np.array([[0.0, -ax[2], ax[1]], [ax[2], 0.0, -ax[0]], [-ax[1], ax[0], 0.0]])
+            Rd = np.eye(3) + np.sin(ang) * K + (1.0 - np.cos(ang)) * (K @ K)
+            out[b, s, :9] = (Rd @ base[s, :9].reshape(3, 3)).reshape(9)
+            out[b, s, 9:] = base[s, 9:] + d
+    return out
+
+
+def world_tables(table, frames, se3):
+    """The B robot tables a batch with `HipOcp.set_obstacle_placements(frames, se3)` solves on: entry b is `table` with the
+    placement of every listed frame replaced by se3[b][slot] (every other frame untouched) -- one table per instance for a
+    checker that has no batch of worlds."""
+    import dataclasses
+
+    ids = [table.frame_id(f) for f in frames]
+    se3 = np.asarray(se3, dtype=float)
+    assert se3.ndim == 3 and se3.shape[1:] == (len(ids), 12), f"se3: expected [B][{len(ids)}][12], got {se3.shape}"
+    out = []
+    for b in range(se3.shape[0]):
+        fp = np.asarray(table.frame_placement, dtype=float).reshape(-1, 12).copy()
+        fp[ids] = se3[b]
+        out.append(dataclasses.replace(table, frame_placement=fp))
+    return out
+
+
 SENSITIVITY_INERTIA_ENTRIES = ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2))
 
 

@@ -515,6 +515,34 @@ int agx_ocp_set_plant_inertials(agx_ocp *ocp, const double *mass, const double *
  * afterwards, the inertials being constant across steps.                                                              */
 int agx_ocp_set_model_inertials(agx_ocp *ocp, const double *mass, const double *com, const double *inertia,
                                 const double *armature);
+/* The OBSTACLES, per instance: instance b evaluates every collision-distance cost row and constraint row that names a listed
+ * frame with that frame placed at se3[b][slot] (a Monte-Carlo study over obstacle poses, a fleet of cells with different
+ * fixtures, a sweep of a moving obstacle's predicted pose, domain randomisation of the scene).
+ * frames [n_frames]: ids of WORLD-FIXED geometry frames of the handle's model (frame_parent < 0, a radius or a box).
+ * se3 [B][n_frames][12]: host memory in the layout of frame_placement (rotation row-major 9, then translation 3), one placement
+ * per instance and listed frame.  Rotations are not checked for orthonormality, as in agx_ocp_set_geom_placement.
+ * n_frames == 0 with both pointers NULL clears the table (accepted on a handle that has none): from then on exactly the
+ * launches of a handle that never had one.
+ * While set: frames that are not listed keep the model's placement, later agx_ocp_set_geom_placement calls on them included;
+ * a listed frame ignores agx_ocp_set_geom_placement until the table is cleared -- that call still updates the model, and
+ * after a clear the latest model placement applies.
+ * READS the table -- everything that evaluates a collision distance of the problem, chains and trees: the derivative pass of
+ * every solve and MPC step (eight-lane and one-lane kernels, running and terminal nodes, wide cost sets, line-search trial
+ * points included), agx_ocp_calc_diff / agx_ocp_direction / agx_ocp_qp_tiles, the constraint evaluation of constrained
+ * problems (narrow and wide sets) and the distance agx_ocp_get_residuals returns for a collision row.
+ * STAYS on the model's table -- functions of the handle's table, or the planner, which knows the nominal scene only:
+ * agx_model_frame_placement, agx_model_frame_jacobian and the trajectory generators.
+ * Combines with agx_ocp_set_model_inertials (the running-node derivative kernels then read both tables) and with
+ * agx_ocp_set_plant_inertials.
+ * Refused, each with the entry point and the offending item in agx_last_error, the handle exactly as it was: null or
+ * inconsistent arguments; a frame out of range; a frame attached to a joint (it moves with the robot: its placement is
+ * relative to that joint and stays the model's); a frame that carries no geometry; a frame listed twice; a non-finite entry
+ * (instance and frame are named).
+ * Scope: models of at most 7 joints after padding; a handle at the 16 / 30 / 32 capacities refuses the call.
+ * The upload waits for the solver stream, then runs in it.  The call ends the tile carry of agx_ocp_mpc_step (the next step
+ * runs the full derivative pass); the carry resumes afterwards, the placements being constant across steps.  ADMM multipliers
+ * are left alone (agx_ocp_reset_duals).                                                                                 */
+int agx_ocp_set_obstacle_placements(agx_ocp *ocp, int n_frames, const int32_t *frames, const double *se3);
 /* The resident initial state x0 [B][nx] (measured state of the next step).          */
 int agx_ocp_download_x0(agx_ocp *ocp, double *x0);
 
