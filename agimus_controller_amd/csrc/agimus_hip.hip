@@ -162,13 +162,13 @@ struct agx_ocp {
   bool plant_set = false;
   std::vector<double> plant_stage;  // host image of d_plant (the upload reads it after the setter has returned the caller's arrays)
   // per-instance controller model (agx_ocp_set_model_inertials, 7-joint capacity): agx::InstanceInertials<nv>[B].  While set,
-  // launch_k1, launch_calc_diff_rows, the warm-start shift and the plant-less rollout launch the instantiations that read it.
+  // every launch that evaluates dynamics goes to the instantiation that reads it (with_sources), as does the plant-less rollout.
   double *d_minert = nullptr;
   bool minert_set = false;
   std::vector<double> minert_stage;
   // per-instance obstacle placements (agx_ocp_set_obstacle_placements, 7-joint capacity): one buffer, agx::ObstaclePlacements (the
   // frame -> slot map) followed by se3 [B][n][12].  While set, every launch that evaluates a collision distance goes to the
-  // instantiation that reads it (launch_with_obs); unset, nothing of a launch differs from a handle that never had a table.
+  // instantiation that reads it (with_sources); unset, nothing of a launch differs from a handle that never had a table.
   void *d_obs = nullptr;
   size_t obs_bytes = 0;  // allocated
   bool obs_set = false;
@@ -521,16 +521,25 @@ int ensure_canonical_tiles(agx_ocp *o) {
   return 0;
 }
 
-// A handle with per-instance obstacle placements: f(sources...) with the trailing arguments of the instantiation that reads them --
-// the obstacle table, behind the controller inertials where the kernel evaluates dynamics (running nodes) and the handle has them.
-// src_t names the template pack of such an instantiation from the arguments.
+// Per-instance sources.  The 7-joint kernels that evaluate dynamics or a collision distance end in a template pack: empty,
+// InstanceInertials<NV> (agx_ocp_set_model_inertials), ObstaclePlacements (agx_ocp_set_obstacle_placements) or both in that order,
+// one more argument each (agx_device.hpp: pack_has, pack_ptr, world_of).  with_sources calls f(sources...) with the trailing
+// arguments of the instantiation a launch takes: the inertials where the kernel evaluates dynamics (INERT: running nodes) and the
+// handle has them, the table where it evaluates a collision distance (OBS) and the handle has one.  A handle with neither reaches
+// f(): the kernel on the model's own tables, as do the larger capacities, whose setters refuse.  src_t names the pack from the
+// arguments.  Every launch of such a kernel goes through here once; DESIGN.md has the table of flags per kernel.
 template <class P>
 using src_t = std::remove_const_t<std::remove_pointer_t<P>>;
-template <int NV, bool READS_INERTIALS, class F>
-void launch_with_obs(agx_ocp *o, F &&f) {
-  const auto *obs = (const agx::ObstaclePlacements *)o->d_obs;
-  if constexpr (READS_INERTIALS) if (o->minert_set) { f((const agx::InstanceInertials<NV> *)o->d_minert, obs); return; }
-  f(obs);
+template <int NV, bool INERT, bool OBS, class F>
+void with_sources(agx_ocp *o, F &&f) {
+  if constexpr (NV <= 7) {
+    [[maybe_unused]] const auto *inst = (const agx::InstanceInertials<NV> *)o->d_minert;
+    [[maybe_unused]] const auto *obs = (const agx::ObstaclePlacements *)o->d_obs;
+    if constexpr (INERT && OBS) if (o->minert_set && o->obs_set) return f(inst, obs);
+    if constexpr (INERT) if (o->minert_set) return f(inst);
+    if constexpr (OBS) if (o->obs_set) return f(obs);
+  }
+  f();
 }
 
 int launch_calc_diff_rows(agx_ocp *o, bool masked, bool running_only) {
@@ -539,50 +548,21 @@ int launch_calc_diff_rows(agx_ocp *o, bool masked, bool running_only) {
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
     const long long units = (long long)o->B * o->T;
-    const int grid = (int)((units + 63) / 64);
-    if constexpr (NV <= 7) if (o->obs_set) {  // per-instance obstacle placements: both node types carry collision rows
-      const DevState *stm = masked ? o->d_state : nullptr;
-      auto both = [&](auto GENc) {
-        constexpr bool GEN = decltype(GENc)::value;
-        launch_with_obs<NV, true>(o, [&](auto... src) {
-          hipLaunchKernelGGL((agx::k_calc_diff<NV, CH, GEN, src_t<decltype(src)>...>), dim3(grid), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt,
-                             o->d_xs, o->d_us, o->rv, o->d_tiles, stm, src...);
+    const DevState *stm = masked ? o->d_state : nullptr;
+    auto both = [&](auto GENc) {
+      constexpr bool GEN = decltype(GENc)::value;
+      with_sources<NV, true, true>(o, [&](auto... src) {
+        hipLaunchKernelGGL((agx::k_calc_diff<NV, CH, GEN, src_t<decltype(src)>...>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model,
+                           o->d_ocp, o->d_dt, o->d_xs, o->d_us, o->rv, o->d_tiles, stm, src...);
+      });
+      if (!running_only)
+        with_sources<NV, false, true>(o, [&](auto... src) {
+          hipLaunchKernelGGL((agx::k_calc_diff_term<NV, CH, GEN, src_t<decltype(src)>...>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model,
+                             o->d_ocp, o->d_xs, o->rv, o->d_tiles, stm, src...);
         });
-        if (!running_only)
-          launch_with_obs<NV, false>(o, [&](auto... src) {
-            hipLaunchKernelGGL((agx::k_calc_diff_term<NV, CH, GEN, src_t<decltype(src)>...>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model,
-                               o->d_ocp, o->d_xs, o->rv, o->d_tiles, stm, src...);
-          });
-      };
-      if (o->general) both(std::true_type()); else both(std::false_type());
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-    // per-instance controller inertials: the running nodes from the instantiations that read them (terminal nodes carry costs only)
-    [[maybe_unused]] const auto *inst = (const agx::InstanceInertials<NV> *)o->d_minert;
-    if constexpr (NV <= 7) if (o->general) {
-      if (o->minert_set)
-        hipLaunchKernelGGL((agx::k_calc_diff<NV, CH, true>), dim3(grid), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
-                           o->d_us, o->rv, o->d_tiles, masked ? o->d_state : nullptr, inst);
-      else
-      hipLaunchKernelGGL((agx::k_calc_diff<NV, CH, true>), dim3(grid), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
-                         o->d_us, o->rv, o->d_tiles, masked ? o->d_state : nullptr);
-      if (running_only) { HIPCHK(hipGetLastError()); return 0; }
-      hipLaunchKernelGGL((agx::k_calc_diff_term<NV, CH, true>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
-                         o->d_xs, o->rv, o->d_tiles, masked ? o->d_state : nullptr);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-    const bool with_inst = NV <= 7 && o->minert_set;  // (the larger capacities have no such instantiation: the setter refuses them)
-    if constexpr (NV <= 7) if (with_inst)
-      hipLaunchKernelGGL((agx::k_calc_diff<NV, CH>), dim3(grid), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
-                         o->d_us, o->rv, o->d_tiles, masked ? o->d_state : nullptr, inst);
-    if (!with_inst)
-    hipLaunchKernelGGL((agx::k_calc_diff<NV, CH>), dim3(grid), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
-                       o->d_us, o->rv, o->d_tiles, masked ? o->d_state : nullptr);
-    if (running_only) { HIPCHK(hipGetLastError()); return 0; }
-    hipLaunchKernelGGL((agx::k_calc_diff_term<NV, CH>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
-                       o->d_xs, o->rv, o->d_tiles, masked ? o->d_state : nullptr);
+    };
+    if constexpr (NV <= 7) { if (o->general) both(std::true_type()); else both(std::false_type()); }  // (GEN: 7 joints only)
+    else both(std::false_type());
     HIPCHK(hipGetLastError());
     return 0;
   });
@@ -600,119 +580,55 @@ int launch_k1(agx_ocp *o, bool running_only, bool term_only, int phase, bool com
     const long long units = (long long)o->B * o->T;
     const double *xs_in = phase ? o->d_xs + (size_t)o->B * (o->T + 1) * o->nx : o->d_xs;
     const double *us_in = phase ? o->d_us + (size_t)o->B * o->T * o->nu : o->d_us;
-    // per-instance controller inertials (agx_ocp_set_model_inertials): the running nodes go to the instantiations that read
-    // them; the terminal kernels evaluate costs only and are today's
-    [[maybe_unused]] const auto *inst = (const agx::InstanceInertials<NV> *)o->d_minert;
-    // per-instance obstacle placements (agx_ocp_set_obstacle_placements): the instantiations that read the table, both node
-    // types.  The eight-lane kernel without a collision row evaluates no distance (a wide cost set keeps its pairs in
-    // k_cost_pairs): it stays on the launches below.
-    if constexpr (NV <= 7) if (o->obs_set) {
-      const bool lanes8 = !o->general && CH && o->k1_lanes && o->lanes_ok;
-      if (lanes8 && o->lanes_coll) {
-        const long long run_nodes = compact ? (long long)o->B * (o->T > 1 ? 2 : 1) : units;
-        const int n_run = (int)((run_nodes * 8 + 63) / 64), n_term = (int)(((long long)o->B * 8 + 63) / 64), cp = compact ? 1 : 0;
-        if (o->k1_fused && !term_only && !running_only) {
-          launch_with_obs<NV, true>(o, [&](auto... src) {
-            hipLaunchKernelGGL((agx::k_calc_qp_lj_all<NV, true, src_t<decltype(src)>...>), dim3(n_run + n_term), dim3(64), 0, o->stream, o->d_model,
-                               o->d_ocp_k1, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, n_run, phase, cp, src...);
-          });
-        } else {
-          if (!term_only)
-            launch_with_obs<NV, true>(o, [&](auto... src) {
-              hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, false, true, src_t<decltype(src)>...>), dim3(n_run), dim3(64), 0, o->stream, o->d_model,
-                                 o->d_ocp_k1, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp, src...);
-            });
-          if (!running_only)
-            launch_with_obs<NV, false>(o, [&](auto... src) {
-              hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, true, true, src_t<decltype(src)>...>), dim3(n_term), dim3(64), 0, o->stream, o->d_model,
-                                 o->d_ocp_k1, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp, src...);
-            });
-        }
-        HIPCHK(hipGetLastError());
-        return 0;
-      }
-      if (!lanes8) {  // one lane per node
-        auto both = [&](auto GENc) {
-          constexpr bool GEN = decltype(GENc)::value;
-          double *auxg = GEN ? o->d_auxg : nullptr;
-          if (!term_only)
-            launch_with_obs<NV, true>(o, [&](auto... src) {
-              hipLaunchKernelGGL((agx::k_calc_qp<NV, CH, GEN, src_t<decltype(src)>...>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream,
-                                 o->d_model, o->d_ocp, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, auxg, phase, src...);
-            });
-          if (!running_only)
-            launch_with_obs<NV, false>(o, [&](auto... src) {
-              hipLaunchKernelGGL((agx::k_calc_qp_term<NV, CH, GEN, src_t<decltype(src)>...>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model,
-                                 o->d_ocp, xs_in, o->rv, o->d_qt, o->d_aux, o->d_state, auxg, phase, src...);
-            });
-        };
-        if (o->general) both(std::true_type()); else both(std::false_type());
-        HIPCHK(hipGetLastError());
-        return 0;
-      }
-    }
-    if constexpr (NV <= 7) if (o->general) {
-      if (!term_only && o->minert_set)
-        hipLaunchKernelGGL((agx::k_calc_qp<NV, CH, true>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
-                           o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, o->d_auxg, phase, inst);
-      else if (!term_only)
-        hipLaunchKernelGGL((agx::k_calc_qp<NV, CH, true>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
-                           o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, o->d_auxg, phase);
-      if (!running_only)
-        hipLaunchKernelGGL((agx::k_calc_qp_term<NV, CH, true>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
-                           xs_in, o->rv, o->d_qt, o->d_aux, o->d_state, o->d_auxg, phase);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-    bool lanes = false;
-    if constexpr (NV <= 7) lanes = CH && o->k1_lanes && o->lanes_ok;
-    if constexpr (NV <= 7) if (lanes) {
-      const long long run_nodes = compact ? (long long)o->B * (o->T > 1 ? 2 : 1) : units;
-      const int n_run = (int)((run_nodes * 8 + 63) / 64), n_term = (int)(((long long)o->B * 8 + 63) / 64), cp = compact ? 1 : 0;
-#define AGX_LAUNCH_LJ(COLL)                                                                                                              \
-  do {                                                                                                                                   \
-    if (o->k1_fused && !term_only && !running_only) { /* both node types in one launch */                                                \
-      if (o->minert_set)                                                                                                                 \
-        hipLaunchKernelGGL((agx::k_calc_qp_lj_all<NV, COLL>), dim3(n_run + n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1,     \
-                           o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, n_run, phase, cp, inst);                        \
-      else                                                                                                                               \
-      hipLaunchKernelGGL((agx::k_calc_qp_lj_all<NV, COLL>), dim3(n_run + n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1, o->d_dt, \
-                         xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, n_run, phase, cp);                                         \
-    } else {                                                                                                                             \
-      if (!term_only && o->minert_set)                                                                                                   \
-        hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, false, COLL>), dim3(n_run), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1, o->d_dt,     \
-                           xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp, inst);                                        \
-      else if (!term_only)                                                                                                               \
-        hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, false, COLL>), dim3(n_run), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1, o->d_dt,     \
-                           xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp);                                              \
-      if (!running_only)                                                                                                                 \
-        hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, true, COLL>), dim3(n_term), dim3(64), 0, o->stream, o->d_model, o->d_ocp_k1, o->d_dt,     \
-                           xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp);                                              \
-    }                                                                                                                                    \
-  } while (0)
-      if (o->lanes_coll) AGX_LAUNCH_LJ(true); else AGX_LAUNCH_LJ(false);
-#undef AGX_LAUNCH_LJ
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
     if constexpr (NV > 8) {
       // large models: one workgroup per node, running and terminal nodes in one launch (agx_big_k1.hpp)
-      (void)lanes; (void)running_only;
       if (term_only) return 0;  // the launch of the running nodes (profiled path) already covered the terminal ones
       launch_wg(o, [&](auto PRc) {
         hipLaunchKernelGGL((agx::k_calc_qp_wg<NV, decltype(PRc)::value>), dim3((int)(units + o->B)), dim3(256), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, xs_in,
                          us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase);
       });
-    } else if (!lanes) {
-      if (!term_only && o->minert_set)
-        hipLaunchKernelGGL((agx::k_calc_qp<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
-                           o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, (double *)nullptr, phase, inst);
-      else if (!term_only)
-        hipLaunchKernelGGL((agx::k_calc_qp<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
-                           o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, (double *)nullptr, phase);
-      if (!running_only)
-        hipLaunchKernelGGL((agx::k_calc_qp_term<NV, CH>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
-                           xs_in, o->rv, o->d_qt, o->d_aux, o->d_state, (double *)nullptr, phase);
+    } else if (NV <= 7 && !o->general && CH && o->k1_lanes && o->lanes_ok) {
+      const long long run_nodes = compact ? (long long)o->B * (o->T > 1 ? 2 : 1) : units;
+      const int n_run = (int)((run_nodes * 8 + 63) / 64), n_term = (int)(((long long)o->B * 8 + 63) / 64), cp = compact ? 1 : 0;
+      auto lanes8 = [&](auto COLLc) {
+        // OBS = COLL: without a collision row the kernel evaluates no distance and never takes the table, even when one is set
+        constexpr bool COLL = decltype(COLLc)::value;
+        if (o->k1_fused && !term_only && !running_only) {  // both node types in one launch
+          with_sources<NV, true, COLL>(o, [&](auto... src) {
+            hipLaunchKernelGGL((agx::k_calc_qp_lj_all<NV, COLL, src_t<decltype(src)>...>), dim3(n_run + n_term), dim3(64), 0, o->stream, o->d_model,
+                               o->d_ocp_k1, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, n_run, phase, cp, src...);
+          });
+          return;
+        }
+        if (!term_only)
+          with_sources<NV, true, COLL>(o, [&](auto... src) {
+            hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, false, COLL, src_t<decltype(src)>...>), dim3(n_run), dim3(64), 0, o->stream, o->d_model,
+                               o->d_ocp_k1, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp, src...);
+          });
+        if (!running_only)
+          with_sources<NV, false, COLL>(o, [&](auto... src) {
+            hipLaunchKernelGGL((agx::k_calc_qp_lj<NV, true, COLL, src_t<decltype(src)>...>), dim3(n_term), dim3(64), 0, o->stream, o->d_model,
+                               o->d_ocp_k1, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase, cp, src...);
+          });
+      };
+      if constexpr (NV <= 7) { if (o->lanes_coll) lanes8(std::true_type()); else lanes8(std::false_type()); }
+    } else {  // one lane per node
+      auto both = [&](auto GENc) {
+        constexpr bool GEN = decltype(GENc)::value;
+        double *auxg = GEN ? o->d_auxg : nullptr;
+        if (!term_only)
+          with_sources<NV, true, true>(o, [&](auto... src) {
+            hipLaunchKernelGGL((agx::k_calc_qp<NV, CH, GEN, src_t<decltype(src)>...>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream,
+                               o->d_model, o->d_ocp, o->d_dt, xs_in, us_in, o->rv, o->d_qt, o->d_aux, o->d_state, auxg, phase, src...);
+          });
+        if (!running_only)
+          with_sources<NV, false, true>(o, [&](auto... src) {
+            hipLaunchKernelGGL((agx::k_calc_qp_term<NV, CH, GEN, src_t<decltype(src)>...>), dim3((o->B + 63) / 64), dim3(64), 0, o->stream, o->d_model,
+                               o->d_ocp, xs_in, o->rv, o->d_qt, o->d_aux, o->d_state, auxg, phase, src...);
+          });
+      };
+      if constexpr (NV <= 7) { if (o->general) both(std::true_type()); else both(std::false_type()); }  // (GEN: 7 joints only)
+      else both(std::false_type());
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -811,27 +727,21 @@ int launch_step(agx_ocp *o, int iter, int max_iter, int mode, bool with_node_kkt
     (void)CH;
     const long long nodes = (long long)o->B * (o->T + 1);
     double *xs_t = o->d_xs + (size_t)o->B * (o->T + 1) * o->nx, *us_t = o->d_us + (size_t)o->B * o->T * o->nu;
-    if constexpr (NV <= 7) if (o->general) {
-      if (with_node_kkt)
-        hipLaunchKernelGGL((agx::k_node_kkt_gen<NV>), dim3((int)((nodes + 63) / 64)), dim3(64), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
-                           o->d_auxg, o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
-      if (with_step)
-        hipLaunchKernelGGL((agx::k_sqp_head<NV>), dim3(o->B), dim3(128), 0, o->stream, o->d_ocp, o->d_xs, o->d_us, o->d_dx, o->d_du, xs_t, us_t,
-                           o->d_nodestat, o->d_state, iter, max_iter, mode, o->d_ndone, host_words(o, false, seq));
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
     if (with_node_kkt) {
-      if constexpr (NV <= 7)
-        hipLaunchKernelGGL((agx::k_node_kkt<NV>), dim3((int)((nodes * 8 + 255) / 256)), dim3(256), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
-                           o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
-      else
+      if constexpr (NV <= 7) {
+        if (o->general)
+          hipLaunchKernelGGL((agx::k_node_kkt_gen<NV>), dim3((int)((nodes + 63) / 64)), dim3(64), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
+                             o->d_auxg, o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
+        else
+          hipLaunchKernelGGL((agx::k_node_kkt<NV>), dim3((int)((nodes * 8 + 255) / 256)), dim3(256), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
+                             o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
+      } else
         hipLaunchKernelGGL((agx::k_node_kkt_big<NV>), dim3((int)((nodes + 1) / 2)), dim3(64), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
                            o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
     }
-    if (!with_step) { HIPCHK(hipGetLastError()); return 0; }
-    hipLaunchKernelGGL((agx::k_sqp_head<NV>), dim3(o->B), dim3(128), 0, o->stream, o->d_ocp, o->d_xs, o->d_us, o->d_dx, o->d_du, xs_t, us_t,
-                       o->d_nodestat, o->d_state, iter, max_iter, mode, o->d_ndone, host_words(o, false, seq));
+    if (with_step)
+      hipLaunchKernelGGL((agx::k_sqp_head<NV>), dim3(o->B), dim3(128), 0, o->stream, o->d_ocp, o->d_xs, o->d_us, o->d_dx, o->d_du, xs_t, us_t,
+                         o->d_nodestat, o->d_state, iter, max_iter, mode, o->d_ndone, host_words(o, false, seq));
     HIPCHK(hipGetLastError());
     return 0;
   });
@@ -977,28 +887,17 @@ template <int NV, bool CH>
 void launch_con_eval(agx_ocp *o, const double *xs, const double *us, int phase) {
   if constexpr (NV <= 7) {
     const long long nodes = (long long)o->B * (o->T + 1);
-    if (o->obs_set) {  // per-instance obstacle placements: the same three kernels, reading the table
-      const auto *obs = (const agx::ObstaclePlacements *)o->d_obs;
+    with_sources<NV, false, true>(o, [&](auto... src) {
       if (o->con_wide)
-        hipLaunchKernelGGL((agx::k_con_eval_pairs<NV, agx::ObstaclePlacements>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model,
-                           o->d_ocp, xs, us, o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase, obs);
+        hipLaunchKernelGGL((agx::k_con_eval_pairs<NV, src_t<decltype(src)>...>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model,
+                           o->d_ocp, xs, us, o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase, src...);
       else if (CH && o->con_lanes)
-        hipLaunchKernelGGL((agx::k_con_eval_lj<NV, agx::ObstaclePlacements>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model,
-                           o->d_ocp, xs, us, o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase, obs);
+        hipLaunchKernelGGL((agx::k_con_eval_lj<NV, src_t<decltype(src)>...>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model,
+                           o->d_ocp, xs, us, o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase, src...);
       else
-        hipLaunchKernelGGL((agx::k_con_eval<NV, CH, agx::ObstaclePlacements>), dim3((int)((nodes + 63) / 64)), dim3(64), 0, o->stream, o->d_model,
-                           o->d_ocp, xs, us, o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase, obs);
-      return;
-    }
-    if (o->con_wide)
-      hipLaunchKernelGGL((agx::k_con_eval_pairs<NV>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, xs, us,
-                         o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase);
-    else if (CH && o->con_lanes)
-      hipLaunchKernelGGL((agx::k_con_eval_lj<NV>), dim3((int)((nodes * 8 + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, xs, us, o->d_cg,
-                         o->d_cjac, o->d_nodestat, o->d_state, phase);
-    else
-      hipLaunchKernelGGL((agx::k_con_eval<NV, CH>), dim3((int)((nodes + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, xs, us, o->d_cg,
-                         o->d_cjac, o->d_nodestat, o->d_state, phase);
+        hipLaunchKernelGGL((agx::k_con_eval<NV, CH, src_t<decltype(src)>...>), dim3((int)((nodes + 63) / 64)), dim3(64), 0, o->stream, o->d_model,
+                           o->d_ocp, xs, us, o->d_cg, o->d_cjac, o->d_nodestat, o->d_state, phase, src...);
+    });
   }
 }
 
@@ -2251,11 +2150,11 @@ int agx_ocp_shift_warmstart(agx_ocp *o) {
         hipLaunchKernelGGL((agx::k_integrate_wg<NV, decltype(PRc)::value>), dim3(o->B * (int)o->shift_nodes.size()), dim3(256), 0, o->stream, o->d_model, o->dt[0], o->d_xs,
                            o->d_us, o->d_xs + n, o->d_shift_nodes, (int)o->shift_nodes.size(), o->T);
       });
-    } else if (o->minert_set)  // the re-integrated nodes follow the instance's own model
-      hipLaunchKernelGGL((agx::k_shift<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us,
-                         (const agx::InstanceInertials<NV> *)o->d_minert);
-    else
-    hipLaunchKernelGGL((agx::k_shift<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us);
+    } else
+      with_sources<NV, true, false>(o, [&](auto... src) {
+        hipLaunchKernelGGL((agx::k_shift<NV, CH, src_t<decltype(src)>...>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
+                           o->d_dt, o->d_xs, o->d_us, src...);
+      });
     hipLaunchKernelGGL(agx::k_shift_commit, dim3((int)((n + 255) / 256)), dim3(256), 0, o->stream, o->d_xs, o->d_us, o->B, o->T, o->nx, o->nu);
     HIPCHK(hipGetLastError());
     return 0;
@@ -2377,13 +2276,10 @@ int agx_ocp_get_residuals(agx_ocp *o, int row, double *out) {
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
     const long long units = (long long)o->B * o->T;
-    bool with_obs = false;
-    if constexpr (NV <= 7) with_obs = o->obs_set;  // the distance of a collision row at the instance's own placements
-    if constexpr (NV <= 7) if (with_obs)
-      hipLaunchKernelGGL((agx::k_residuals<NV, CH, agx::ObstaclePlacements>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
-                         o->d_xs, o->d_us, o->rv, row, o->d_scratch, (const agx::ObstaclePlacements *)o->d_obs);
-    if (!with_obs)
-    hipLaunchKernelGGL((agx::k_residuals<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, o->d_xs, o->d_us, o->rv, row, o->d_scratch);
+    with_sources<NV, false, true>(o, [&](auto... src) {
+      hipLaunchKernelGGL((agx::k_residuals<NV, CH, src_t<decltype(src)>...>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp,
+                         o->d_xs, o->d_us, o->rv, row, o->d_scratch, src...);
+    });
     HIPCHK(hipGetLastError());
     return 0;
   });
@@ -3144,14 +3040,11 @@ int agx_ocp_mpc_step(agx_ocp *o, int k0, int max_iter, int first) {
         constexpr int NV = decltype(NVc)::value;
         constexpr bool CH = decltype(CHc)::value;
         if constexpr (NV <= 8) {
-          if (o->minert_set)
-            hipLaunchKernelGGL((agx::k_mpc_prologue<NV, CH>), dim3(o->B), dim3(128), lds, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
-                               o->d_us, o->d_x0, o->d_state, o->d_ndone, first == 0 ? 1 : 0, carry ? 1 : 0, o->head,
-                               (int *)((char *)o->d_ocp + offsetof(DevOcp, head)), (const agx::InstanceInertials<NV> *)o->d_minert);
-          else
-          hipLaunchKernelGGL((agx::k_mpc_prologue<NV, CH>), dim3(o->B), dim3(128), lds, o->stream, o->d_model, o->d_ocp, o->d_dt, o->d_xs,
-                             o->d_us, o->d_x0, o->d_state, o->d_ndone, first == 0 ? 1 : 0, carry ? 1 : 0, o->head,
-                             (int *)((char *)o->d_ocp + offsetof(DevOcp, head)));
+          with_sources<NV, true, false>(o, [&](auto... src) {
+            hipLaunchKernelGGL((agx::k_mpc_prologue<NV, CH, src_t<decltype(src)>...>), dim3(o->B), dim3(128), lds, o->stream, o->d_model, o->d_ocp,
+                               o->d_dt, o->d_xs, o->d_us, o->d_x0, o->d_state, o->d_ndone, first == 0 ? 1 : 0, carry ? 1 : 0, o->head,
+                               (int *)((char *)o->d_ocp + offsetof(DevOcp, head)), src...);
+          });
           HIPCHK(hipGetLastError());
         }
         return 0;

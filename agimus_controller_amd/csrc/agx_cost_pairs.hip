@@ -13,22 +13,16 @@ int agx_cost_pairs_launch(int dest, void *stream, long long nodes, const DevMode
                           const void *obs) {
   const dim3 grid((unsigned)((nodes * 8 + 63) / 64)), blk(64);
   hipStream_t s = (hipStream_t)stream;
-  if (obs) {
-    const auto *ob = (const agx::ObstaclePlacements *)obs;
-    if (dest == agx::kPairsToQp)
-      hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsToQp>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which, ob);
-    else if (dest == agx::kPairsToCanonical)
-      hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsToCanonical>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which, ob);
-    else
-      hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsDistance>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which, ob);
-    return (int)hipGetLastError();
-  }
-  if (dest == agx::kPairsToQp)
-    hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsToQp>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which);
-  else if (dest == agx::kPairsToCanonical)
-    hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsToCanonical>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which);
-  else
-    hipLaunchKernelGGL((agx::k_cost_pairs<7, agx::kPairsDistance>), grid, blk, 0, s, m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which);
+  auto launch = [&](auto... src) {  // src: nothing, or the table behind the template pack it names
+    auto to = [&](auto DESTc) {
+      hipLaunchKernelGGL((agx::k_cost_pairs<7, decltype(DESTc)::value, std::remove_const_t<std::remove_pointer_t<decltype(src)>>...>), grid, blk, 0, s,
+                         m, o, w, dts, xs, *rv, out, auxs, st, phase, sel, which, src...);
+    };
+    if (dest == agx::kPairsToQp) to(std::integral_constant<int, agx::kPairsToQp>());
+    else if (dest == agx::kPairsToCanonical) to(std::integral_constant<int, agx::kPairsToCanonical>());
+    else to(std::integral_constant<int, agx::kPairsDistance>());
+  };
+  if (obs) launch((const agx::ObstaclePlacements *)obs); else launch();
   return (int)hipGetLastError();
 }
 
