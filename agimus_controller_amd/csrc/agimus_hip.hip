@@ -104,6 +104,7 @@ struct agx_ocp {
   int mx2_S = 0;
   double *d_mx2_elem = nullptr, *d_mx2_bnd = nullptr, *d_mx2_cl = nullptr;  // [2][B][S][3][256] segment elements, [2][B][S][256] boundary value functions, [B][S][256] transitions under the gains
   bool k1_fused = true;     // AGX_K1_FUSED=0: running and terminal nodes of the derivative pass as two launches (profiling)
+  bool node_kkt_wide = true;  // AGX_NODE_KKT_WIDE=0: nv <= 7 node shares by k_node_kkt (a wait per group of loads) instead of k_node_kkt_ahead
   // Tile carry across MPC steps: the running-node tiles live in a ring (tile_slot, agx_kernels.hpp) whose
   // origin advances with every carried agx_ocp_mpc_step, so that the first derivative pass of a step evaluates nodes 0, T - 1
   // and T only.  7-joint capacity, eight-lane derivative kernel, unconstrained, MFMA-layout sweeps, one dt for every node.
@@ -732,6 +733,9 @@ int launch_step(agx_ocp *o, int iter, int max_iter, int mode, bool with_node_kkt
         if (o->general)
           hipLaunchKernelGGL((agx::k_node_kkt_gen<NV>), dim3((int)((nodes + 63) / 64)), dim3(64), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
                              o->d_auxg, o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
+        else if (o->node_kkt_wide)
+          hipLaunchKernelGGL((agx::k_node_kkt_ahead<NV>), dim3((int)((nodes + 7) / 8)), dim3(64), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
+                             o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
         else
           hipLaunchKernelGGL((agx::k_node_kkt<NV>), dim3((int)((nodes * 8 + 255) / 256)), dim3(256), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
                              o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
@@ -1506,6 +1510,7 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   if (const char *e = getenv("AGX_FOLD_PUBLISH")) o->fold_publish = (e[0] != '0');
   if (const char *e = getenv("AGX_ADMM_LOOP")) { o->admm_loop = (e[0] != '0'); o->admm_loop_always = (e[0] == '2'); }
   if (const char *e = getenv("AGX_K1_FUSED")) o->k1_fused = (e[0] != '0');
+  if (const char *e = getenv("AGX_NODE_KKT_WIDE")) o->node_kkt_wide = (e[0] != '0');
   if (const char *e = getenv("AGX_TILE_CARRY")) o->tile_carry = (e[0] != '0');
   o->T = d->horizon; o->B = batch; o->device = device;
   {

@@ -925,6 +925,91 @@ AGX_UNROLL_NV
   }
 }
 
+// The same pass with every load issued ahead of its use (default for nv <= 7; AGX_NODE_KKT_WIDE=0 runs the kernel above).
+// k_node_kkt reads a node's share of the aux tile behind eight dependent waits (status, dx, f, the M / tq / tv rows, Luu, the
+// Lqq rows, Lvv, cost): the compiler keeps the exec-masked loads of `if (jl)` where they stand.  Here one wave per workgroup
+// loads the small per-lane operands at clamped indices (selected afterwards, as the values were before) and the 30 rows of the
+// aux tile into registers right after the status word -- one wait instead of eight, 36 loads per lane in flight -- and then runs
+// the arithmetic of k_node_kkt unchanged: same products, same row sums (transpose_reduce8), same butterflies -> the same bits.
+// (Staging the tiles of the wave's eight nodes in LDS with 16-byte loads was measured too and was slower: DESIGN.md section 5.)
+template <int NV>
+__global__ void __launch_bounds__(64) k_node_kkt_ahead(const DevOcp *__restrict__ op, const double *__restrict__ qts,
+                                                       const double *__restrict__ auxs, const double *__restrict__ dxs,
+                                                       const double *__restrict__ wss, double *__restrict__ dus,
+                                                       double *__restrict__ nodestat, const DevState *__restrict__ st) {
+  constexpr int NX = 2 * NV;
+  typedef QT<NV> Q;
+  typedef AUX<NV> A;
+  const DevOcp &o = *op;
+  const int T = o.T;
+  const int l8 = threadIdx.x & 7;
+  const long long n_nodes = (long long)o.B * (T + 1);
+  const long long node = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 3;
+  const bool ok = node < n_nodes;
+  const long long nid = ok ? node : 0;
+  const int b = (int)(nid / (T + 1)), t = (int)(nid % (T + 1));
+  const DevState &S = st[b];
+  const bool act = ok && !S.done;
+  if (!__any(act)) return;  // wave of finished instances
+  const double preg = S.preg, dreg = S.dreg;
+  const bool jl = l8 < NV;
+  const int jj = jl ? l8 : 0;
+  const long long sid = (long long)b * (T + 1) + tile_slot(o, t);
+  const double *qt = qts + sid * Q::SIZE;
+  const double *ax = auxs + sid * A::SIZE;
+  const double *dx = dxs + nid * NX;
+  // every load of the wave in flight before the first wait
+  const double dq_l = dx[jj], dv_l = dx[NV + jj];
+  double wj_l = 0.0;
+  if (t < T) wj_l = wss[((long long)b * T + t) * NV + jj];
+  const double fq_l = qt[Q::f + jj], fv_l = qt[Q::f + NV + jj];  // (the terminal tile carries zeros there)
+  const double cost = qt[Q::cost];
+  double rM[8] = {}, rtq[8] = {}, rtv[8] = {}, rLqq[8] = {}, rLuu = 0.0, rLvv = 0.0;
+  if (t < T) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      rM[i] = ax[A::M + i * A::LD + l8]; rtq[i] = ax[A::tq + i * A::LD + l8]; rtv[i] = ax[A::tv + i * A::LD + l8];
+    }
+    rLuu = ax[A::Luu + l8];
+  }
+  if (t > 0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) rLqq[i] = ax[A::Lqq + i * A::LD + l8];
+    rLvv = ax[A::Lvv + l8];
+  }
+  const double dq = jl ? dq_l : 0.0, dv = jl ? dv_l : 0.0;
+  double kkt = 0.0, gap = 0.0;
+  if (t < T) {
+    const double wj = jl ? wj_l : 0.0;
+    const double fq = jl ? fq_l : 0.0, fv = jl ? fv_l : 0.0;
+    kkt = fmax(fabs(fq), fabs(fv));
+    gap = fabs(fq) + fabs(fv);
+    double pr[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pr[i] = (i < NV) ? rM[i] * wj + rtq[i] * dq + rtv[i] * dv : 0.0;
+    const double du = transpose_reduce8(pr, l8);
+    if (jl) {
+      if (act) dus[((long long)b * T + t) * NV + l8] = du;
+      kkt = fmax(kkt, fabs((rLuu + preg) * du));
+    }
+  }
+  if (t > 0) {
+    double pr[8];
+AGX_UNROLL_NV
+    for (int i = 0; i < 8; ++i) pr[i] = (i < NV) ? rLqq[i] * dq : 0.0;
+    const double hq = transpose_reduce8(pr, l8);
+    if (jl) kkt = fmax(kkt, fmax(fabs(hq + dreg * dq), fabs((rLvv + dreg) * dv)));
+  }
+  // group max / sum (fixed order: deterministic)
+  kkt = fmax(kkt, dpp_xor4(kkt)); kkt = fmax(kkt, dpp_xor2(kkt)); kkt = fmax(kkt, dpp_xor1(kkt));
+  gap += dpp_xor4(gap); gap += dpp_xor2(gap); gap += dpp_xor1(gap);
+  if (act && l8 == 0) {
+    double *ns = nodestat + nid * 4;
+    ns[0] = kkt; ns[1] = cost; ns[2] = gap;
+    if (!o.has_con) ns[3] = 0.0;  // as k_node_kkt
+  }
+}
+
 // ---------------------------------------------------------------------------
 // K4: the step of one SQP iteration (SolverCSQP::solve after computeDirection).
 //
@@ -985,6 +1070,18 @@ __device__ __forceinline__ void write_trial_iterate(const DevOcp &o, int b, doub
   for (int e = threadIdx.x; e < (T + 1) * NX; e += blockDim.x) xs_t[ox + e] = xs[ox + e] + alpha * dxs[ox + e];
   for (int e = threadIdx.x; e < T * NU; e += blockDim.x) us_t[ou + e] = us[ou + e] + alpha * dus[ou + e];
 }
+// The copies at the end of k_sqp_head / k_sqp_accept do not depend on the decision, only their stores do: the first N
+// workgroup strides of a vector of n doubles are loaded into registers ahead of the reduction and the barrier (N strides of
+// 128 threads hold the iterate of a 7-joint problem up to T = 108; whatever lies beyond is copied after the decision as before).
+constexpr int kPrefX = 12, kPrefU = 6;
+template <int N>
+__device__ __forceinline__ void prefetch_strided(double (&r)[N], const double *__restrict__ p, int n) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const int e = threadIdx.x + k * blockDim.x;
+    r[k] = e < n ? p[e] : 0.0;
+  }
+}
 
 // Hand-off to the host without a launch of its own (small batches, where every launch is ~ 4 us of a 200 us step): every
 // workgroup of a kernel arrives at a counter when it is done, the last one stores the counters the host waits for, then the
@@ -1030,6 +1127,18 @@ __global__ void __launch_bounds__(128) k_sqp_head(const DevOcp *__restrict__ op,
   if (S.done) {  // (uniform over the workgroup)
     if (tid == 0) arrive_and_publish(n_done, hw);
     return;
+  }
+  // operands of the first trial iterate, in flight during the reduction and the decision (only where a line search can start)
+  constexpr int NX = 2 * NV, NU = NV;
+  const int nxs = (T + 1) * NX, nus = T * NU;
+  const long long ox = (long long)b * nxs, ou = (long long)b * nus;
+  const bool ls = (mode & 1) && !(mode & 4);
+  double px[kPrefX], pdx[kPrefX], pu[kPrefU], pdu[kPrefU];
+  if (ls) {
+    prefetch_strided(px, xs + ox, nxs);
+    prefetch_strided(pdx, dxs + ox, nxs);
+    prefetch_strided(pu, us + ou, nus);
+    prefetch_strided(pdu, dus + ou, nus);
   }
   double kkt = 0.0, csum = 0.0, gsum = 0.0, vsum = 0.0;
   for (int t = tid; t <= T; t += blockDim.x) {
@@ -1078,7 +1187,20 @@ __global__ void __launch_bounds__(128) k_sqp_head(const DevOcp *__restrict__ op,
     arrive_and_publish(n_done, hw);  // (the host wants the finished count; the trial iterate below is for the next kernel of the stream)
   }
   __syncthreads();
-  if (flag) write_trial_iterate<NV>(o, b, 1.0, xs, us, dxs, dus, xs_t, us_t);
+  if (!flag) return;  // (flag != 0 only with ls)
+  // write_trial_iterate at alpha = 1 out of the prefetched operands
+#pragma unroll
+  for (int k = 0; k < kPrefX; ++k) {
+    const int e = tid + k * blockDim.x;
+    if (e < nxs) xs_t[ox + e] = px[k] + 1.0 * pdx[k];
+  }
+  for (int e = tid + kPrefX * blockDim.x; e < nxs; e += blockDim.x) xs_t[ox + e] = xs[ox + e] + 1.0 * dxs[ox + e];
+#pragma unroll
+  for (int k = 0; k < kPrefU; ++k) {
+    const int e = tid + k * blockDim.x;
+    if (e < nus) us_t[ou + e] = pu[k] + 1.0 * pdu[k];
+  }
+  for (int e = tid + kPrefU * blockDim.x; e < nus; e += blockDim.x) us_t[ou + e] = us[ou + e] + 1.0 * dus[ou + e];
 }
 
 // After the derivative pass at the trial points: totals of the trial (cost and dynamics gaps out of the new tiles, violation
@@ -1106,6 +1228,12 @@ __global__ void __launch_bounds__(128) k_sqp_accept(const DevOcp *__restrict__ o
     if (tid == 0) arrive_and_publish(n_done, hw);
     return;
   }
+  // the trial iterate, in flight during the reduction and the decision: an accepted step (the usual end) only stores it
+  const int nxs = (T + 1) * NX, nus = T * NU;
+  const long long ox = (long long)b * nxs, ou = (long long)b * nus;
+  double px[kPrefX], pu[kPrefU];
+  prefetch_strided(px, xs_t + ox, nxs);
+  prefetch_strided(pu, us_t + ou, nus);
   double pc = 0.0, pg = 0.0, pv = 0.0;
   for (int t = tid; t <= T; t += blockDim.x) {
     const double *qt = qts + ((long long)b * (T + 1) + tile_slot(o, t)) * Q::SIZE;
@@ -1151,9 +1279,18 @@ __global__ void __launch_bounds__(128) k_sqp_accept(const DevOcp *__restrict__ o
   }
   __syncthreads();
   if (flag == 1) {
-    const long long ox = (long long)b * (T + 1) * NX, ou = (long long)b * T * NU;
-    for (int e = tid; e < (T + 1) * NX; e += blockDim.x) xs[ox + e] = xs_t[ox + e];
-    for (int e = tid; e < T * NU; e += blockDim.x) us[ou + e] = us_t[ou + e];
+#pragma unroll
+    for (int k = 0; k < kPrefX; ++k) {
+      const int e = tid + k * blockDim.x;
+      if (e < nxs) xs[ox + e] = px[k];
+    }
+    for (int e = tid + kPrefX * blockDim.x; e < nxs; e += blockDim.x) xs[ox + e] = xs_t[ox + e];
+#pragma unroll
+    for (int k = 0; k < kPrefU; ++k) {
+      const int e = tid + k * blockDim.x;
+      if (e < nus) us[ou + e] = pu[k];
+    }
+    for (int e = tid + kPrefU * blockDim.x; e < nus; e += blockDim.x) us[ou + e] = us_t[ou + e];
   } else if (flag == 2) {
     write_trial_iterate<NV>(o, b, s_alpha, xs, us, dxs, dus, xs_t, us_t);
   }
