@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "agx_ocp_set_plant_inertials", "agx_model_sensitivity", "agx_ocp_cost_wide", "agx_ocp_set_model_inertials",
     "agx_traj_stream_create", "agx_traj_stream_append", "agx_traj_stream_release", "agx_traj_stream_range",
     "agx_traj_stream_joins", "agx_traj_stream_timing", "agx_ocp_set_obstacle_placements",
+    "agx_ocp_set_first_pack", "agx_ocp_first_pack_counts", "agx_ocp_handoff_counts",
 ]  # fmt: skip
 
 
@@ -287,8 +288,10 @@ class HipOcp:
         return xs, us, K, st
 
     def download_first(self, want_status=True, copy=True):
-        """us[0], K[0], xs[1] (+ status) of every instance: one packed transfer into the handle's
-        pinned buffer.  copy=False returns views into that buffer, valid until the next call."""
+        """us[0], K[0], xs[1] (+ status) of every instance out of the handle's pinned buffer.  Instances that converge write
+        their record into it during the solve; when all of them did, this call launches and waits for nothing, otherwise one
+        pack kernel fills the buffer.  copy=False returns views into that buffer, valid until the next call that solves
+        (solve, solve_resident, mpc_step) or packs (download_first)."""
         ptr = C.POINTER(C.c_double)()
         stride = C.c_int(0)
         _chk(lib().agx_ocp_first_packed(self._h, C.byref(ptr), C.byref(stride)))
@@ -316,6 +319,23 @@ class HipOcp:
             else:
                 st = {name: q[:, k] for k, name in enumerate(names)}  # views (float64) into the pinned buffer
         return us0, K0, x1, st
+
+    def set_first_pack(self, in_solve: bool = True):
+        """False: no first-node record is written during a solve; download_first always packs with a launch of its own."""
+        _chk(lib().agx_ocp_set_first_pack(self._h, 1 if in_solve else 0))
+
+    def first_pack_counts(self):
+        """(download_first calls served from records written during the solve, calls served by the pack kernel)."""
+        a, b = C.c_longlong(0), C.c_longlong(0)
+        _chk(lib().agx_ocp_first_pack_counts(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def handoff_counts(self):
+        """(solves that ended on the hand-off right behind the head of the step, instances whose tiles the next mpc_step may
+        inherit as the last solve published it)."""
+        a, b = C.c_longlong(0), C.c_int(0)
+        _chk(lib().agx_ocp_handoff_counts(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def set_geom_placement(self, frame: int, se3_12):
         """OCPBaseCroco.update_geometry_placement (ocp_base_croco.py:110-132) for a geometry frame."""

@@ -147,7 +147,9 @@ struct agx_ocp {
   int *d_ndone = nullptr;
   // pinned, fine-grained (coherent) mapped host words, 64 bit each: [0] finished-instance count, [1] its sequence
   // stamp, [2] stamp of the packed results, [3] scratch value, [4] ADMM converged count, [5] its stamp, [6] / [7] line-search
-  // trials handed on / iterations ended with stale tiles, [8] instances with tiles the next MPC step may inherit.
+  // trials handed on / iterations ended with stale tiles, [8] instances with tiles the next MPC step may inherit, [9] instances
+  // whose first-node record k_sqp_head has packed, [10] stamp of the hand-off right behind the head of large batches and
+  // [11] / [12] / [13] its finished / inheritable / packed counts.
   // Stamps are 64-bit and only ever grow (no wrap in practice); slots start at ~0, which no stamp takes.
   unsigned long long *h_ndone = nullptr;
   unsigned long long *h_ndone_dev = nullptr;  // the same words as the device sees them (mapped host memory)
@@ -156,6 +158,13 @@ struct agx_ocp {
   bool poll = true;  // AGX_HOST_POLL=0: stream-ordered copies + synchronize instead of polled mapped words
   double *d_first = nullptr, *h_first = nullptr;  // packed first-node results [B][first_stride], device / pinned host
   int first_stride = 0;
+  // First-node records packed during the solve (k_sqp_head, agx_ocp_set_first_pack): once the block exists the head gets it, and
+  // a solve that every instance ended by packing its record leaves it fresh -- agx_ocp_first_packed then returns it as it is.
+  bool first_in_solve = true;
+  bool first_fresh = false;  // the block holds the results of the last solve and nothing has touched xs / us / K / the state since
+  int n_packed = 0;          // records packed in the running solve, as last published
+  long long first_served[2] = {0, 0};  // agx_ocp_first_packed calls served from the fresh block / by k_pack_first
+  long long early_exits = 0;  // SQP loops that ended on the hand-off right behind the head, without waiting for the trial round (agx_ocp_handoff_counts)
   double *d_scratch = nullptr;
   size_t scratch_bytes = 0;
   // plant of the closed loop (agx_ocp_set_plant_inertials): agx::PlantInertials<nv>[B], read by k_plant_rollout only
@@ -709,18 +718,26 @@ int launch_riccati(agx_ocp *o, int forward, bool pair = false, int iter = 0, con
 // K3 (node shares of the KKT residual, cost, gaps; du) and the head of the step: instance totals, convergence test and the
 // first trial iterate of the line search (the caller runs the trial rounds: line_search_rounds).
 agx::HostWords host_words(agx_ocp *o, bool line_search_counters, unsigned long long seq) {
-  agx::HostWords hw{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  agx::HostWords hw{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   if (!o->poll || !o->fold_publish || seq == 0) return hw;
   hw.done = o->h_ndone_dev + 0;
   if (line_search_counters) { hw.handed = o->h_ndone_dev + 6; hw.stale = o->h_ndone_dev + 7; }
   hw.carry = o->h_ndone_dev + 8;
+  hw.packed = o->h_ndone_dev + 9;
   hw.seq = o->h_ndone_dev + 1;
   hw.stamp = seq;
   return hw;
 }
 
-// `seq` != 0 (small batches): the head's last workgroup hands the finished-instance count to the host under that stamp
-int launch_step(agx_ocp *o, int iter, int max_iter, int mode, bool with_node_kkt = true, bool with_step = true, unsigned long long seq = 0) {
+// the block the head of the step packs first-node records into: the mapped block of agx_ocp_first_packed once it exists
+double *first_block(const agx_ocp *o) {
+  return (o->first_in_solve && o->poll && o->first_stride == o->nu + o->nu * o->nx + o->nx + 8) ? o->d_first : nullptr;
+}
+
+// `seq` != 0 (small batches): the head's last workgroup hands the finished-instance count to the host under that stamp.
+// `pack` (solve_resident): converging instances pack their first-node record (first_block).
+int launch_step(agx_ocp *o, int iter, int max_iter, int mode, bool with_node_kkt = true, bool with_step = true, unsigned long long seq = 0,
+                bool pack = false) {
   if (o->T + 1 > 512) return fail("step kernel supports horizons up to 511 nodes");
   return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
     constexpr int NV = decltype(NVc)::value;
@@ -745,7 +762,8 @@ int launch_step(agx_ocp *o, int iter, int max_iter, int mode, bool with_node_kkt
     }
     if (with_step)
       hipLaunchKernelGGL((agx::k_sqp_head<NV>), dim3(o->B), dim3(128), 0, o->stream, o->d_ocp, o->d_xs, o->d_us, o->d_dx, o->d_du, xs_t, us_t,
-                         o->d_nodestat, o->d_state, iter, max_iter, mode, o->d_ndone, host_words(o, false, seq));
+                         o->d_nodestat, o->d_state, iter, max_iter, mode, o->d_ndone, host_words(o, false, seq), o->d_Kout,
+                         pack ? first_block(o) : nullptr, o->first_stride);
     HIPCHK(hipGetLastError());
     return 0;
   });
@@ -1061,9 +1079,11 @@ int admm_direction(agx_ocp *o, bool prefactor = false) {
 }
 
 // Every entry point that changes an input of the derivative pass, the iterate or the tiles outside agx_ocp_mpc_step: the next
-// step runs the full pass, with the tiles back in node order.
+// step runs the full pass, with the tiles back in node order.  The same calls may change what the first-node block was packed
+// from during the last solve (iterate, gains, state): the next agx_ocp_first_packed packs again.
 int carry_invalidate(agx_ocp *o) {
   o->carry_armed = false;
+  o->first_fresh = false;
   if (o->head != 0) {
     o->head = 0;
     HIPCHK(hipMemsetAsync((char *)o->d_ocp + offsetof(DevOcp, head), 0, sizeof(int), o->stream));
@@ -1159,7 +1179,11 @@ int traj_locate(agx_ocp *o, const char *fn, const char *what, int k, int span, i
 // trials grows, i.e. when somebody rejected a step length -- the same again.  The finished-instance count comes back
 // under the same stamp, and so does the counter of iterations that ended with every trial rejected: only then does the
 // next iteration need a derivative pass of its own (`need_k1`); after an accepted trial the tiles are already there.
-int line_search_rounds(agx_ocp *o, int it, int max_iter, bool *need_k1, int *n_done_out) {
+// `head_seq` != 0 (large batches, from the second iteration on): the counters the head left were published right behind it under
+// that stamp (slots 10 .. 13).  The first round is queued without asking, as ever; then the host looks at the head's words, and
+// when they say that every instance has finished it leaves without waiting for the round: its launches find nobody searching,
+// change no counter, and stay queued ahead of whatever the stream gets next.
+int line_search_rounds(agx_ocp *o, int it, int max_iter, bool *need_k1, int *n_done_out, unsigned long long head_seq = 0) {
   double *xs_t = o->d_xs + (size_t)o->B * (o->T + 1) * o->nx, *us_t = o->d_us + (size_t)o->B * o->T * o->nu;
   for (int round = 0; round < 10; ++round) {
     if (o->prof && round == 0 && it == 0) {  // the kernel the roofline is quoted on, timed alone: running nodes of the trial pass of the first
@@ -1195,11 +1219,22 @@ int line_search_rounds(agx_ocp *o, int it, int max_iter, bool *need_k1, int *n_d
       if (wait_stamp(o, 1, seq)) return -1;  // stored by the last workgroup of k_sqp_accept
     } else if (o->poll) {
       hipLaunchKernelGGL(agx::k_publish3, dim3(1), dim3(1), 0, o->stream, o->d_ndone, o->h_ndone_dev + 0, o->h_ndone_dev + 6, o->h_ndone_dev + 7,
-                         o->h_ndone_dev + 8, o->h_ndone_dev + 1, seq);
+                         o->h_ndone_dev + 8, o->h_ndone_dev + 9, o->h_ndone_dev + 1, seq);
       HIPCHK(hipGetLastError());
+      if (round == 0 && head_seq != 0) {
+        if (wait_stamp(o, 10, head_seq)) return -1;
+        const int done_at_head = (int)__atomic_load_n(o->h_ndone + 11, __ATOMIC_ACQUIRE);
+        if (done_at_head >= o->B) {
+          *n_done_out = done_at_head;
+          o->n_carriable = (int)__atomic_load_n(o->h_ndone + 12, __ATOMIC_ACQUIRE);
+          o->n_packed = (int)__atomic_load_n(o->h_ndone + 13, __ATOMIC_ACQUIRE);
+          o->early_exits += 1;
+          return 0;
+        }
+      }
       if (wait_stamp(o, 1, seq)) return -1;
     } else {
-      o->h_ndone[0] = 0; o->h_ndone[6] = 0; o->h_ndone[7] = 0; o->h_ndone[8] = 0;
+      o->h_ndone[0] = 0; o->h_ndone[6] = 0; o->h_ndone[7] = 0; o->h_ndone[8] = 0; o->h_ndone[9] = 0;  // (no mapped block on this path: nothing is packed in the solve)
       HIPCHK(hipMemcpyAsync(o->h_ndone + 8, o->d_ndone + 6, sizeof(int), hipMemcpyDeviceToHost, o->stream));
       HIPCHK(hipMemcpyAsync(o->h_ndone, o->d_ndone, sizeof(int), hipMemcpyDeviceToHost, o->stream));
       HIPCHK(hipMemcpyAsync(o->h_ndone + 6, o->d_ndone + 3, sizeof(int), hipMemcpyDeviceToHost, o->stream));
@@ -1210,6 +1245,7 @@ int line_search_rounds(agx_ocp *o, int it, int max_iter, bool *need_k1, int *n_d
     const unsigned handed = (unsigned)__atomic_load_n(o->h_ndone + 6, __ATOMIC_ACQUIRE);
     const unsigned stale = (unsigned)__atomic_load_n(o->h_ndone + 7, __ATOMIC_ACQUIRE);
     o->n_carriable = (int)__atomic_load_n(o->h_ndone + 8, __ATOMIC_ACQUIRE);
+    o->n_packed = (int)__atomic_load_n(o->h_ndone + 9, __ATOMIC_ACQUIRE);
     const bool more = handed != o->ls_handed;
     if (stale != o->ls_stale) *need_k1 = true;
     o->ls_handed = handed;
@@ -1225,6 +1261,10 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
   if (max_iter <= 0) max_iter = 1000;
   o->last_max_iter = max_iter;
   o->n_carriable = -1;
+  o->first_fresh = false;
+  o->n_packed = 0;
+  const bool packing = first_block(o) != nullptr;
+  bool cut = false;  // the loop ended on a quorum or the time limit with instances unfinished
   auto t0 = std::chrono::steady_clock::now();
   if (!prologue_done) {  // k_mpc_prologue has reset the state and pinned x0 already
     if (reset_state(o)) return -1;
@@ -1267,8 +1307,18 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
     const bool last = it + 1 == max_iter;
     if (prof_mark(o, 2, true)) return -1;
     const unsigned long long seq_head = ++o->seq;
-    if (launch_step(o, it, max_iter, 1, !o->has_con, true, seq_head)) return -1;
+    if (launch_step(o, it, max_iter, 1, !o->has_con, true, seq_head, pair && packing)) return -1;
     if (prof_mark(o, 2, false)) return -1;
+    // Large batches, from the second iteration on (where warm-started MPC steps converge): what the head left, to the host
+    // under a stamp of its own right behind it -- the trial round below is still queued without asking, but the host no longer
+    // waits for it when the head has finished everyone (line_search_rounds).
+    unsigned long long seq_early = 0;
+    if (o->poll && !o->fold_publish && !o->prof && !o->no_empty && it >= 1) {
+      seq_early = ++o->seq;
+      hipLaunchKernelGGL(agx::k_publish3, dim3(1), dim3(1), 0, o->stream, o->d_ndone, o->h_ndone_dev + 11, (unsigned long long *)nullptr, (unsigned long long *)nullptr, o->h_ndone_dev + 12,
+                         o->h_ndone_dev + 13, o->h_ndone_dev + 10, seq_early);
+      HIPCHK(hipGetLastError());
+    }
     int n_done = 0;
     // The trial passes overwrite the tiles of this iterate.  Where the loop may end right after this iteration without a
     // paired gains sweep (iteration cap, time limit, quorum), the sweep that yields the reported gains runs first --
@@ -1284,28 +1334,32 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
       if (wait_stamp(o, 1, seq_head)) return -1;
       n_done = (int)__atomic_load_n(o->h_ndone, __ATOMIC_ACQUIRE);
       o->n_carriable = (int)__atomic_load_n(o->h_ndone + 8, __ATOMIC_ACQUIRE);
+      o->n_packed = (int)__atomic_load_n(o->h_ndone + 9, __ATOMIC_ACQUIRE);
       searching = n_done < o->B;
     } else if (o->prof || o->no_empty) {  // timing / profiling runs: no launches that find nothing to do
       if (read_int(o, o->d_ndone, 0, 1, &n_done)) return -1;
       searching = n_done < o->B;
       if (!searching && read_int(o, o->d_ndone + 6, 8, 1, &o->n_carriable)) return -1;  // (the line search would have brought it)
+      if (!searching && pair && packing && read_int(o, o->d_ndone + 7, 9, 1, &o->n_packed)) return -1;  // (likewise)
     }
-    if (searching && line_search_rounds(o, it, max_iter, &need_k1, &n_done)) return -1;
+    if (searching && line_search_rounds(o, it, max_iter, &need_k1, &n_done, seq_early)) return -1;
     if (last) { need_fixup = need_fixup || !pair; break; }
     if (!pair && n_done > prev_done) need_fixup = true;
     prev_done = n_done;
     if (n_done >= quorum_count(o->B, o->quorum_sqp)) {
-      if (n_done < o->B) o->last_max_iter = it + 1;  // the stragglers stop here: iterations that really ran
+      if (n_done < o->B) { o->last_max_iter = it + 1; cut = true; }  // the stragglers stop here: iterations that really ran
       break;
     }
     if (max_time > 0.0) {
       // SolverCSQP max_solve_time (ocp_base_croco.py:70-71): checked once per SQP iteration; unfinished instances
       // report the iterations that really ran
       const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      if (el > max_time) { need_fixup = need_fixup || !pair; o->last_max_iter = it + 1; break; }
+      if (el > max_time) { need_fixup = need_fixup || !pair; o->last_max_iter = it + 1; cut = true; break; }
     }
   }
   if (!o->has_con && need_fixup && launch_gains(o, 2)) return -1;  // instances whose last direction has no gains sweep yet
+  // every instance packed its first-node record where it converged, and nothing has been launched on the gains since
+  o->first_fresh = packing && o->n_packed == o->B && !need_fixup && !cut;
   return prof_collect(o);
 }
 
@@ -1841,6 +1895,7 @@ int agx_ocp_set_quorum(agx_ocp *o, double sqp_fraction, double qp_fraction) {
 int agx_ocp_reset_duals(agx_ocp *o) {
   if (!o) return fail("null handle");
   if (set_device(o)) return -1;
+  o->first_fresh = false;  // (the state changes)
   if (o->has_con) HIPCHK(hipMemsetAsync(o->d_y, 0, sizeof(double) * (size_t)o->B * (o->T + 1) * o->con_cs, o->stream));
   hipLaunchKernelGGL(agx::k_reset_rho, dim3((o->B + 255) / 256), dim3(256), 0, o->stream, o->d_state, o->B);
   HIPCHK(hipGetLastError());
@@ -2078,16 +2133,22 @@ int agx_ocp_first_packed(agx_ocp *o, const double **host, int *stride) {
     o->first_stride = FS;
   }
   const long long n = (long long)o->B * FS;
-  hipLaunchKernelGGL(agx::k_pack_first, dim3((int)((n + 255) / 256)), dim3(256), 0, o->stream, o->d_us, o->d_Kout, o->d_xs, o->d_state,
-                     o->d_first, o->B, o->T, o->nx, o->nu, o->last_max_iter);
-  HIPCHK(hipGetLastError());
-  if (o->poll) {
-    const unsigned long long seq = ++o->seq;
-    if (publish(o, 3, 2, o->d_ndone, seq)) return -1;
-    if (wait_stamp(o, 2, seq)) return -1;
+  if (o->first_fresh && first_block(o)) {
+    // every instance packed its record where it converged (k_sqp_head), and the host has seen the stamp behind those stores
+    o->first_served[0] += 1;
   } else {
-    HIPCHK(hipMemcpyAsync(o->h_first, o->d_first, sizeof(double) * n, hipMemcpyDeviceToHost, o->stream));
-    HIPCHK(hipStreamSynchronize(o->stream));
+    o->first_served[1] += 1;
+    hipLaunchKernelGGL(agx::k_pack_first, dim3((int)((n + 255) / 256)), dim3(256), 0, o->stream, o->d_us, o->d_Kout, o->d_xs, o->d_state,
+                       o->d_first, o->B, o->T, o->nx, o->nu, o->last_max_iter);
+    HIPCHK(hipGetLastError());
+    if (o->poll) {
+      const unsigned long long seq = ++o->seq;
+      if (publish(o, 3, 2, o->d_ndone, seq)) return -1;
+      if (wait_stamp(o, 2, seq)) return -1;
+    } else {
+      HIPCHK(hipMemcpyAsync(o->h_first, o->d_first, sizeof(double) * n, hipMemcpyDeviceToHost, o->stream));
+      HIPCHK(hipStreamSynchronize(o->stream));
+    }
   }
   if (o->padded) {  // [us0 | K0 | x1 | status] of the caller's nvu joints
     const int nv = o->nv, nvu = o->nvu, FSu = nvu + nvu * 2 * nvu + 2 * nvu + 8;
@@ -2128,9 +2189,30 @@ int agx_ocp_download_first(agx_ocp *o, double *us0, double *K0, double *x1, agx_
   return 0;
 }
 
+int agx_ocp_set_first_pack(agx_ocp *o, int in_solve) {
+  if (!o) return fail("null handle");
+  o->first_in_solve = in_solve != 0;
+  return 0;
+}
+
+int agx_ocp_first_pack_counts(agx_ocp *o, long long *served_in_solve, long long *served_by_launch) {
+  if (!o) return fail("null handle");
+  if (served_in_solve) *served_in_solve = o->first_served[0];
+  if (served_by_launch) *served_by_launch = o->first_served[1];
+  return 0;
+}
+
+int agx_ocp_handoff_counts(agx_ocp *o, long long *early_exits, int *n_carriable) {
+  if (!o) return fail("null handle");
+  if (early_exits) *early_exits = o->early_exits;
+  if (n_carriable) *n_carriable = o->n_carriable;
+  return 0;
+}
+
 int agx_ocp_solve(agx_ocp *o, const double *x0, const double *xs_ws, const double *us_ws, int max_iter, double max_time,
                   double *xs, double *us, double *K, agx_status *st) {
   if (!o || !x0 || !xs_ws || !us_ws) return fail("agx_ocp_solve: null argument");
+  o->first_fresh = false;
   if (agx_ocp_upload_x0(o, x0)) return -1;
   if (agx_ocp_upload_warmstart(o, xs_ws, us_ws)) return -1;  // (ends the tile carry: carry_invalidate)
   if (solve_resident(o, max_iter, max_time)) return -1;
@@ -3023,6 +3105,7 @@ int agx_model_sensitivity(agx_ocp *o, int n, double dt, const double *x, const d
 int agx_ocp_mpc_step(agx_ocp *o, int k0, int max_iter, int first) {
   if (!o) return fail("null handle");
   if (set_device(o)) return -1;
+  o->first_fresh = false;  // (the prologue moves the iterate; solve_resident decides anew)
   if (agx_traj_set_window(o, k0)) return -1;
   bool prologue_done = false;
   // Tile carry: this step follows the previous one by one sample on the resident trajectory, so after the shift below node t

@@ -1089,7 +1089,7 @@ __device__ __forceinline__ void prefetch_strided(double (&r)[N], const double *_
 // one-thread kernel (a thousand workgroups arriving at one counter cost the B = 1024 step more than the launch: measured).
 // One thread per workgroup calls this, after its last write to the counters.
 struct HostWords {
-  unsigned long long *done, *handed, *stale, *carry, *seq;  // mapped host words (handed / stale may be null)
+  unsigned long long *done, *handed, *stale, *carry, *packed, *seq;  // mapped host words (handed / stale may be null)
   unsigned long long stamp;
 };
 __device__ __forceinline__ void arrive_and_publish(int *__restrict__ counts, const HostWords &hw) {
@@ -1103,6 +1103,7 @@ __device__ __forceinline__ void arrive_and_publish(int *__restrict__ counts, con
   if (hw.handed) __hip_atomic_store(hw.handed, (unsigned long long)(unsigned)__hip_atomic_load(counts + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (hw.stale) __hip_atomic_store(hw.stale, (unsigned long long)(unsigned)__hip_atomic_load(counts + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(hw.carry, (unsigned long long)(unsigned)__hip_atomic_load(counts + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(hw.packed, (unsigned long long)(unsigned)__hip_atomic_load(counts + 7, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __threadfence_system();
   __hip_atomic_store(hw.seq, hw.stamp, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -1113,13 +1114,22 @@ __device__ __forceinline__ void arrive_and_publish(int *__restrict__ counts, con
 // restatement gets there through NaNs in the trial merit), all ten step lengths count as rejected at once.
 // mode bit0: run the line search; without it only the totals (test hook).  mode bit2: timing mode (nothing committed).
 // n_done[0]: finished instances.
+// FIRST-NODE RECORD WHERE THE INSTANCE FINISHES (`first` != nullptr: the mapped block of agx_ocp_first_packed, `first_stride`
+// doubles per instance).  An unconstrained instance that converges here in an iteration whose gains sweep rode along
+// (S.gains_iter == iter: Kout is final) has everything a controller consumes on the device already: the workgroup writes
+// [us0 | K0 | x1 | kkt cost merit gap iter qp_iters solved flags] as k_pack_first would and counts itself in n_done[7].  The host
+// takes the block without a launch when every instance of the solve is counted there.  Order for such a workgroup: the stores
+// of the record, a workgroup barrier, then the counters by thread 0 -- behind a system-scope fence where the stamp that lets
+// the host read comes out of this very kernel (arrive_and_publish).
 template <int NV>
 __global__ void __launch_bounds__(128) k_sqp_head(const DevOcp *__restrict__ op, const double *__restrict__ xs, const double *__restrict__ us,
                                                   const double *__restrict__ dxs, const double *__restrict__ dus,
                                                   double *__restrict__ xs_t, double *__restrict__ us_t,
                                                   const double *__restrict__ nodestat, DevState *__restrict__ st, int iter, int max_iter,
-                                                  int mode, int *__restrict__ n_done, HostWords hw) {
+                                                  int mode, int *__restrict__ n_done, HostWords hw, const double *__restrict__ Kout,
+                                                  double *__restrict__ first, int first_stride) {
   __shared__ double red[8];
+  __shared__ double s_words[8];  // status words of a record packed here
   __shared__ int flag;
   const DevOcp &o = *op;
   const int T = o.T, b = blockIdx.x, tid = threadIdx.x;
@@ -1140,6 +1150,16 @@ __global__ void __launch_bounds__(128) k_sqp_head(const DevOcp *__restrict__ op,
     prefetch_strided(pu, us + ou, nus);
     prefetch_strided(pdu, dus + ou, nus);
   }
+  // likewise the first workgroup stride of the record [us0 | K0 | x1 | words] this instance packs if it converges (seven joints: all of it)
+  constexpr int NK = NU * NX, FS = NU + NK + NX + 8;  // (FS == first_stride: the host passes the block only then)
+  const bool may_pack = first != nullptr && !o.has_con && S.gains_iter == iter;  // (uniform over the workgroup)
+  auto record_element = [&](int e) -> double {  // e < FS - 8
+    if (e < NU) return us[ou + e];
+    if (e < NU + NK) return Kout[(long long)b * T * NK + (e - NU)];
+    return xs[ox + NX + (e - NU - NK)];
+  };
+  double prec = 0.0;
+  if (may_pack && tid < FS - 8) prec = record_element(tid);
   double kkt = 0.0, csum = 0.0, gsum = 0.0, vsum = 0.0;
   for (int t = tid; t <= T; t += blockDim.x) {
     const double *ns = nodestat + ((long long)b * (T + 1) + t) * 4;
@@ -1167,9 +1187,15 @@ __global__ void __launch_bounds__(128) k_sqp_head(const DevOcp *__restrict__ op,
     if (!(mode & 4)) S.dir_iter = iter;
     if (!(kk == kk)) S.flags |= 1;
     const bool conv = (kk <= o.tol) && (mode & 1) && !(mode & 4);
-    int what = 0;  // 0: nothing more, 1: line search starts
-    if (conv) { S.solved = 1; S.done = 1; S.iter = iter; S.tiles_ok = 1; atomicAdd(n_done, 1); }  // (the tiles are those of the final iterate)
-    else if ((mode & 1) && !(mode & 4)) {
+    int what = 0;  // 0: nothing more, 1: line search starts, 2: first-node record packed here
+    if (conv) {
+      S.solved = 1; S.done = 1; S.iter = iter; S.tiles_ok = 1; atomicAdd(n_done, 1);  // (the tiles are those of the final iterate)
+      if (may_pack) {
+        what = 2;
+        s_words[0] = kk; s_words[1] = cc; s_words[2] = S.merit; s_words[3] = gg;
+        s_words[4] = iter; s_words[5] = S.qp_iters; s_words[6] = 1; s_words[7] = S.flags;
+      }
+    } else if ((mode & 1) && !(mode & 4)) {
       S.tiles_ok = 0;
       if (dir_fail) { S.flags |= 4; sqp_iteration_end(S, false, 1.0 / 512.0, iter, max_iter, n_done); }
       else {
@@ -1184,10 +1210,27 @@ __global__ void __launch_bounds__(128) k_sqp_head(const DevOcp *__restrict__ op,
     }
     flag = what;
     if ((mode & 1) && !(mode & 4)) count_carriable(S, n_done);
-    arrive_and_publish(n_done, hw);  // (the host wants the finished count; the trial iterate below is for the next kernel of the stream)
+    if (what != 2) arrive_and_publish(n_done, hw);  // (the host wants the finished count; the trial iterate below is for the next kernel of the stream)
   }
   __syncthreads();
-  if (!flag) return;  // (flag != 0 only with ls)
+  if (flag == 2) {
+    double *rec = first + (long long)b * first_stride;
+    if (tid < FS) rec[tid] = tid < FS - 8 ? prec : s_words[tid - (FS - 8)];
+    for (int e = tid + blockDim.x; e < FS; e += blockDim.x)  // capacities above 7 joints: longer than the workgroup
+      rec[e] = e < FS - 8 ? record_element(e) : s_words[e - (FS - 8)];
+    __syncthreads();
+    if (tid == 0) {
+      // The host may read the block once it has seen a stamp behind these stores.  Where that stamp comes out of this kernel
+      // (hw.seq: the last workgroup to arrive stores it) the record is fenced at system scope here; where a later kernel of the
+      // stream publishes (k_publish3, large batches) the end of this kernel orders the stores before it, and a thousand
+      // system-scope fences -- an L2 write-back each -- cost the head more than the pack launch did.
+      if (hw.seq) __threadfence_system();
+      atomicAdd(n_done + 7, 1);
+      arrive_and_publish(n_done, hw);
+    }
+    return;
+  }
+  if (!flag) return;  // (flag == 1 only with ls)
   // write_trial_iterate at alpha = 1 out of the prefetched operands
 #pragma unroll
   for (int k = 0; k < kPrefX; ++k) {
@@ -1301,7 +1344,7 @@ __global__ void __launch_bounds__(128) k_sqp_accept(const DevOcp *__restrict__ o
 // ---------------------------------------------------------------------------
 __global__ void k_reset_state(DevState *st, int B, int *n_done) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b == 0) { n_done[0] = 0; n_done[6] = 0; }
+  if (b == 0) { n_done[0] = 0; n_done[6] = 0; n_done[7] = 0; }
   if (b >= B) return;
   DevState s;
   s.rho_sparse = st[b].rho_sparse; s.con = 0.0; s.admm_conv = 0; s.admm_iter = 0; s.ls_acc = 0; s.admm_refactor = 1;
@@ -1314,14 +1357,16 @@ __global__ void k_reset_state(DevState *st, int B, int *n_done) {
 }
 
 // four words under one stamp: finished instances, line-search trials handed on, iterations ended with stale tiles, instances
-// whose tiles the next MPC step may inherit
+// whose tiles the next MPC step may inherit, instances whose first-node record is packed (k_sqp_head).  The hand-off right
+// behind the head of large batches publishes the words the head can change only (host_handed == host_stale == nullptr).
 __global__ void k_publish3(const int *__restrict__ d_counts, unsigned long long *host_done, unsigned long long *host_handed,
-                           unsigned long long *host_stale, unsigned long long *host_carry, unsigned long long *host_seq,
-                           unsigned long long seq) {
+                           unsigned long long *host_stale, unsigned long long *host_carry, unsigned long long *host_packed,
+                           unsigned long long *host_seq, unsigned long long seq) {
   __hip_atomic_store(host_carry, (unsigned long long)(unsigned)d_counts[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(host_packed, (unsigned long long)(unsigned)d_counts[7], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(host_done, (unsigned long long)(unsigned)d_counts[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(host_handed, (unsigned long long)(unsigned)d_counts[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(host_stale, (unsigned long long)(unsigned)d_counts[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (host_handed) __hip_atomic_store(host_handed, (unsigned long long)(unsigned)d_counts[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (host_stale) __hip_atomic_store(host_stale, (unsigned long long)(unsigned)d_counts[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __threadfence_system();
   __hip_atomic_store(host_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -1520,7 +1565,7 @@ AGX_UNROLL_NV
     X[tid] = x1;
   }
   if (tid == 0) {
-    if (b == 0) { n_done[0] = 0; n_done[6] = 0; *head_out = head; }  // (DevOcp::head: no kernel of this launch reads it)
+    if (b == 0) { n_done[0] = 0; n_done[6] = 0; n_done[7] = 0; *head_out = head; }  // (DevOcp::head: no kernel of this launch reads it)
     DevState s;
     // tile carry (host: this step follows the previous one by one sample, see agx_ocp_mpc_step): the tiles the previous solve
     // left belong to its final iterate and carry the regularisation this solve starts with

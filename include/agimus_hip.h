@@ -272,8 +272,21 @@ int agx_ocp_download_first(agx_ocp *ocp, double *us0, double *K0, double *x1, ag
 /* Same data without the host-side scatter: one device-side pack, one transfer into a pinned buffer
  * owned by the handle.  *host -> [B][*stride] doubles, per instance
  *   us0 (nu) | K0 (nu*ndx, row major) | x1 (nx) | kkt cost merit gap_norm iter qp_iters solved flags;
- * valid until the next call on this handle.                                      */
+ * valid until the next call on this handle that solves (agx_ocp_solve, agx_ocp_solve_resident, agx_ocp_mpc_step) or packs
+ * (this one, agx_ocp_download_first): instances that converge write their record into the same buffer while the solve runs.
+ * When every instance of the last solve did -- each converged in an iteration whose gains sweep rode along, the usual end of a
+ * warm-started MPC step -- and nothing has touched the iterate, the gains or the solver state since, the buffer is returned as
+ * it is, without a launch and without a wait; otherwise one pack kernel fills it as before.                                    */
 int agx_ocp_first_packed(agx_ocp *ocp, const double **host, int *stride);
+/* in_solve = 0: no record is written during a solve, agx_ocp_first_packed always packs with its own launch.  Default 1.       */
+int agx_ocp_set_first_pack(agx_ocp *ocp, int in_solve);
+/* agx_ocp_first_packed / agx_ocp_download_first calls on this handle served from records written during the solve / by the
+ * pack kernel (either pointer may be NULL).                                                                                    */
+int agx_ocp_first_pack_counts(agx_ocp *ocp, long long *served_in_solve, long long *served_by_launch);
+/* Introspection of the host loop (tests): solves of this handle whose SQP loop ended on the counters published right behind the
+ * head of the step, without waiting for the queued trial round (batches above 204), and the number of instances whose derivative
+ * tiles the next agx_ocp_mpc_step may inherit as the last solve published it (-1: not known).  Either pointer may be NULL.       */
+int agx_ocp_handoff_counts(agx_ocp *ocp, long long *early_exits, int *n_carriable);
 
 /* Replaces WarmStartShiftPreviousSolution.shift
  * (warm_start_shift_previous_solution.py:85-109) on the resident solution.     */
