@@ -132,6 +132,34 @@ STATUS_DTYPE = np.dtype(
 assert STATUS_DTYPE.itemsize == C.sizeof(Status)
 
 
+class IterRecord(C.Structure):
+    """agx_iter_record: one SQP iteration of one instance in the per-iteration solver log (agx_ocp_iter_log)."""
+
+    _fields_ = [
+        ("kkt", C.c_double),
+        ("cost", C.c_double),
+        ("merit", C.c_double),
+        ("gap_norm", C.c_double),
+        ("constraint_norm", C.c_double),
+        ("step", C.c_double),
+        ("preg", C.c_double),
+        ("dreg", C.c_double),
+        ("iter", C.c_int32),
+        ("qp_iters", C.c_int32),
+        ("trials", C.c_int32),
+        ("flags", C.c_int32),
+    ]
+
+
+ITER_RECORD_DTYPE = np.dtype([(name, "f8" if ctype is C.c_double else "i4") for name, ctype in IterRecord._fields_])
+assert ITER_RECORD_DTYPE.itemsize == C.sizeof(IterRecord) == 80
+# agx_iter_record.flags
+ITER_CONVERGED = 1  # converged in this iteration
+ITER_DISCARDED = 2  # direction discarded (failed factorisation)
+ITER_REJECTED = 4  # all ten step lengths rejected
+ITER_CUT = 8  # ended by cap / time limit / quorum before a search
+
+
 def tile_doubles(nv: int) -> int:
     """AGX_TILE_DOUBLES(nv): Fx|Fu|f|Lx|Lu|Lxx|Lxu|Luu|cost."""
     return 13 * nv * nv + 5 * nv + 1

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "agx_traj_stream_create", "agx_traj_stream_append", "agx_traj_stream_release", "agx_traj_stream_range",
     "agx_traj_stream_joins", "agx_traj_stream_timing", "agx_ocp_set_obstacle_placements",
     "agx_ocp_set_first_pack", "agx_ocp_first_pack_counts", "agx_ocp_handoff_counts",
+    "agx_ocp_iter_log", "agx_ocp_iter_log_read", "agx_ocp_item_costs", "agx_ocp_carry_counts",
 ]  # fmt: skip
 
 
@@ -58,13 +59,14 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
     the single translation unit instead."""
     hdr = _CSRC.parent.parent / "include" / "agimus_hip.h"
     pairs_src = _CSRC / "agx_cost_pairs.hip"  # the wide-cost-set kernels: a translation unit of their own (see the file)
-    srcs = [_CSRC / "agimus_hip.hip"] + sorted(_CSRC.glob("*.hpp")) + [hdr, _CSRC / "agx_front.py", pairs_src]
+    diag_src = _CSRC / "agx_diag.hip"  # the diagnostics kernels (iteration log, per-item costs): likewise, one unit for every capacity
+    srcs = [_CSRC / "agimus_hip.hip"] + sorted(_CSRC.glob("*.hpp")) + [hdr, _CSRC / "agx_front.py", pairs_src, diag_src]
     if not force and LIB_PATH.exists() and LIB_PATH.stat().st_mtime >= max(s.stat().st_mtime for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
     if os.environ.get("AGX_BUILD_SPLIT", "1") == "0":
-        _run(base + [f"-I{hdr.parent}", "-shared", "-o", str(LIB_PATH), str(srcs[0]), str(pairs_src)], verbose)
+        _run(base + [f"-I{hdr.parent}", "-shared", "-o", str(LIB_PATH), str(srcs[0]), str(pairs_src), str(diag_src)], verbose)
         return LIB_PATH
     import importlib.util
 
@@ -80,6 +82,8 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
     cmd = base + ["-c", f"-I{hdr.parent}", "-DAGX_GROUP=0", "-o", str(obj / "agx_cost_pairs.o"), str(pairs_src)]  # the sizes of group 0
     procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
+    cmd = base + ["-c", f"-I{hdr.parent}", "-o", str(obj / "agx_diag.o"), str(diag_src)]
+    procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
     (obj / "agx_front.cpp").write_text(front.front_source(hdr.read_text()))
     _run(["g++", "-O2", "-std=c++17", "-fPIC", f"-I{hdr.parent}", "-c", "-o", str(obj / "agx_front.o"), str(obj / "agx_front.cpp")], verbose)
     failed = None
@@ -92,7 +96,7 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
     if failed:
         raise failed
     _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB_PATH)] + [str(obj / f"agx_g{g}.o") for g in front.GROUPS]
-         + [str(obj / "agx_cost_pairs.o"), str(obj / "agx_front.o")], verbose)
+         + [str(obj / "agx_cost_pairs.o"), str(obj / "agx_diag.o"), str(obj / "agx_front.o")], verbose)
     return LIB_PATH
 
 
@@ -182,6 +186,7 @@ class HipOcp:
         self.T, self.B = packed_ocp.horizon, int(batch)
         self.stride = packed_ocp.stride
         self.tile = _abi.tile_doubles(self.nv)
+        self._log_cap = 0  # capacity of the per-iteration solver log (iter_log); 0: off
         self._m = C.c_void_p()
         self._h = C.c_void_p()
         _chk(L.agx_model_create(C.byref(self.pm.desc), C.byref(self._m)))
@@ -337,6 +342,12 @@ class HipOcp:
         _chk(lib().agx_ocp_handoff_counts(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def carry_counts(self):
+        """(mpc_step calls whose first derivative pass inherited the previous step's tiles, calls that ran the full pass)."""
+        a, b = C.c_longlong(0), C.c_longlong(0)
+        _chk(lib().agx_ocp_carry_counts(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def set_geom_placement(self, frame: int, se3_12):
         """OCPBaseCroco.update_geometry_placement (ocp_base_croco.py:110-132) for a geometry frame."""
         _chk(lib().agx_ocp_set_geom_placement(self._h, int(frame), _p(_f8(se3_12).reshape(12))))
@@ -386,6 +397,36 @@ class HipOcp:
         nr = _abi.row_nr(self.po.running[row].kind, self.nv)
         out = np.empty((self.B, self.T, nr))
         _chk(lib().agx_ocp_get_residuals(self._h, int(row), _p(out)))
+        return out
+
+    # -- diagnostics --------------------------------------------------------
+    def iter_log(self, capacity: int):
+        """Per-iteration solver log (agx_ocp_iter_log): room for `capacity` records per instance; 0 switches it off.  While on,
+        every solve / solve_resident / mpc_step starts the log afresh; results are the same with the log on or off."""
+        _chk(lib().agx_ocp_iter_log(self._h, int(capacity)))
+        self._log_cap = int(capacity)
+
+    def read_iter_log(self):
+        """(records, n): records [B][capacity] structured array (_abi.ITER_RECORD_DTYPE, record j = SQP iteration j), n [B] the
+        iterations every instance started in the last solve (records at or beyond the capacity are dropped, n still counts
+        them).  `solver_log.SolverLog.from_records` turns the pair into arrays per field and a table."""
+        cap = self._log_cap
+        if cap <= 0:
+            raise HipError("read_iter_log: the log is off (iter_log(capacity))")
+        rec = np.zeros((self.B, cap), dtype=_abi.ITER_RECORD_DTYPE)
+        n = np.zeros(self.B, dtype=np.int32)
+        _chk(lib().agx_ocp_iter_log_read(self._h, _p(rec), _p(n)))
+        return rec, n
+
+    def item_costs(self):
+        """Every cost item of every node on its own at the resident (xs, us) (agx_ocp_item_costs): a dict with
+        cost_r [B][T][Rr], Lx_r [B][T][Rr][nx], Lu_r [B][T][Rr][nu], cost_t [B][Rt], Lx_t [B][Rt][nx]; Rr / Rt: all rows of the
+        running / terminal table.  Differential level: item weight x activation, WITHOUT the factor dt of a running node.  The
+        call only reads (iterate, solver state and tile carry are untouched)."""
+        Rr, Rt = len(self.po.running), len(self.po.terminal)
+        out = {"cost_r": np.empty((self.B, self.T, Rr)), "Lx_r": np.empty((self.B, self.T, Rr, self.nx)),
+               "Lu_r": np.empty((self.B, self.T, Rr, self.nu)), "cost_t": np.empty((self.B, Rt)), "Lx_t": np.empty((self.B, Rt, self.nx))}  # fmt: skip
+        _chk(lib().agx_ocp_item_costs(self._h, _p(out["cost_r"]), _p(out["Lx_r"]), _p(out["Lu_r"]), _p(out["cost_t"]), _p(out["Lx_t"])))
         return out
 
     # -- kernel level -------------------------------------------------------

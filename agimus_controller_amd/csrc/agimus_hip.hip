@@ -25,6 +25,10 @@ extern "C" int agx_cost_pairs_launch(int dest, void *stream, long long nodes, co
 extern "C" int agx_cost_pairs_fill_launch(void *stream, const DevCostWide *w, const double *gw_item, double *traj, long long units, int stride);
 extern "C" int agx_cost_pairs_fill_ring_launch(void *stream, const DevCostWide *w, const double *gw_item, double *traj, int B, int m_new, int end,
                                                int cap, int mirror, int stride);
+// launchers of the diagnostics kernels, likewise (agx_diag.hip)
+extern "C" int agx_diag_iter_log_launch(void *stream, const DevState *st, int B, int it, int phase, agx_iter_record *rec, int *n, int capacity);
+extern "C" int agx_diag_item_costs_launch(void *stream, int nv, int chain, const DevModel *m, const DevRows *rows2, int B, int T, const double *xs,
+                                          const double *us, const RefView *rv, int R, double *cost, double *Lx, double *Lu, const void *obs);
 
 namespace {
 
@@ -164,6 +168,7 @@ struct agx_ocp {
   bool first_fresh = false;  // the block holds the results of the last solve and nothing has touched xs / us / K / the state since
   int n_packed = 0;          // records packed in the running solve, as last published
   long long first_served[2] = {0, 0};  // agx_ocp_first_packed calls served from the fresh block / by k_pack_first
+  long long steps_carried = 0, steps_full = 0;  // agx_ocp_mpc_step calls whose first derivative pass inherited tiles (carry_mode != 0) / ran in full (agx_ocp_carry_counts)
   long long early_exits = 0;  // SQP loops that ended on the hand-off right behind the head, without waiting for the trial round (agx_ocp_handoff_counts)
   double *d_scratch = nullptr;
   size_t scratch_bytes = 0;
@@ -220,6 +225,14 @@ struct agx_ocp {
   struct { int buf = -1, m = 0, end = 0; size_t used = 0; agx::SineParams sp{}; } st_last;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_done = nullptr;
   int last_max_iter = 0;
+  // per-iteration solver log (agx_ocp_iter_log): records [B][log_cap] and counts [B] on the device; log_cap == 0: off, and a solve
+  // launches nothing for it
+  int log_cap = 0;
+  agx_iter_record *d_log = nullptr;
+  int *d_log_n = nullptr;
+  // staging of agx_ocp_item_costs (cost | Lx | Lu of every node and row at the capacity), grown on demand
+  double *d_items = nullptr;
+  size_t items_bytes = 0;
   // in-situ kernel timing (agx_ocp_profile): event pairs around the launches of the SQP loop
   bool prof = false;
   std::vector<hipEvent_t> prof_ev;  // [2 * k] start, [2 * k + 1] stop
@@ -1255,6 +1268,14 @@ int line_search_rounds(agx_ocp *o, int it, int max_iter, bool *need_k1, int *n_d
   return 0;
 }
 
+// Per-iteration solver log: k_iter_log (agx_diag.hip) behind the head (phase 0) and behind the trial rounds (phase 1) of SQP
+// iteration `it`.  Off: nothing is launched.
+int iter_log_mark(agx_ocp *o, int it, int phase) {
+  if (o->log_cap <= 0) return 0;
+  HIPCHK((hipError_t)agx_diag_iter_log_launch((void *)o->stream, o->d_state, o->B, it, phase, o->d_log, o->d_log_n, o->log_cap));
+  return 0;
+}
+
 // The SQP loop of SolverCSQP::solve on the resident buffers.
 // carry_mode (agx_ocp_mpc_step): 0 no instance inherits tiles, 1 some do (k_mpc_prologue has decided: DevState::carry), 2 all do.
 int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done = false, int carry_mode = 0) {
@@ -1270,6 +1291,7 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
     if (reset_state(o)) return -1;
     hipLaunchKernelGGL(agx::k_pin_x0, dim3((o->B * o->nx + 255) / 256), dim3(256), 0, o->stream, o->d_xs, o->d_x0, o->B, o->T, o->nx);
   }
+  if (o->log_cap > 0) HIPCHK(hipMemsetAsync(o->d_log_n, 0, sizeof(int) * (size_t)o->B, o->stream));  // every solve starts the log afresh
   // Every iteration after the first finds its tiles already there (the accepted trial of the line search left them); a
   // derivative pass of its own is needed at the start and after an iteration that ended with every step length rejected.
   bool need_k1 = true;
@@ -1309,6 +1331,7 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
     const unsigned long long seq_head = ++o->seq;
     if (launch_step(o, it, max_iter, 1, !o->has_con, true, seq_head, pair && packing)) return -1;
     if (prof_mark(o, 2, false)) return -1;
+    if (iter_log_mark(o, it, 0)) return -1;  // the evaluation and how the head left every instance, before a trial round moves on
     // Large batches, from the second iteration on (where warm-started MPC steps converge): what the head left, to the host
     // under a stamp of its own right behind it -- the trial round below is still queued without asking, but the host no longer
     // waits for it when the head has finished everyone (line_search_rounds).
@@ -1343,6 +1366,7 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
       if (!searching && pair && packing && read_int(o, o->d_ndone + 7, 9, 1, &o->n_packed)) return -1;  // (likewise)
     }
     if (searching && line_search_rounds(o, it, max_iter, &need_k1, &n_done, seq_early)) return -1;
+    if (iter_log_mark(o, it, 1)) return -1;  // the outcome of the search (queued behind the trial round where the host left it early)
     if (last) { need_fixup = need_fixup || !pair; break; }
     if (!pair && n_done > prev_done) need_fixup = true;
     prev_done = n_done;
@@ -1837,7 +1861,8 @@ void agx_ocp_destroy(agx_ocp *o) {
   if (o->copy_stream) (void)hipStreamSynchronize(o->copy_stream);
   void *ptrs[] = {o->d_mx2_elem, o->d_mx2_bnd, o->d_mx2_cl, o->d_ref_back, o->d_frames_back, o->d_snap, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us, o->d_x0, o->d_tiles, o->d_Kws, o->d_kws, o->d_Kout, o->d_dx,
                   o->d_du, o->d_ref, o->d_frames, o->d_state, o->d_ndone, o->d_scratch, o->d_traj, o->d_pts, o->d_sine, o->d_qt, o->d_aux, o->d_w, o->d_nodestat,
-                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr, o->d_plant, o->d_minert, o->d_cw, o->d_obs};
+                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr, o->d_plant, o->d_minert, o->d_cw, o->d_obs,
+                  o->d_log, o->d_log_n, o->d_items};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (o->h_ndone) (void)hipHostFree(o->h_ndone);
@@ -2209,6 +2234,13 @@ int agx_ocp_handoff_counts(agx_ocp *o, long long *early_exits, int *n_carriable)
   return 0;
 }
 
+int agx_ocp_carry_counts(agx_ocp *o, long long *steps_carried, long long *steps_full) {
+  if (!o) return fail("null handle");
+  if (steps_carried) *steps_carried = o->steps_carried;
+  if (steps_full) *steps_full = o->steps_full;
+  return 0;
+}
+
 int agx_ocp_solve(agx_ocp *o, const double *x0, const double *xs_ws, const double *us_ws, int max_iter, double max_time,
                   double *xs, double *us, double *K, agx_status *st) {
   if (!o || !x0 || !xs_ws || !us_ws) return fail("agx_ocp_solve: null argument");
@@ -2378,6 +2410,83 @@ int agx_ocp_get_residuals(agx_ocp *o, int row, double *out) {
     else HIPCHK(hipMemcpyAsync(out, o->d_scratch, sizeof(double) * cnt, hipMemcpyDeviceToHost, o->stream));
   }
   HIPCHK(hipStreamSynchronize(o->stream));
+  return 0;
+}
+
+int agx_ocp_iter_log(agx_ocp *o, int capacity) {
+  if (!o) return fail("null handle");
+  if (capacity < 0) return fail("agx_ocp_iter_log: negative capacity");
+  if (set_device(o)) return -1;
+  HIPCHK(hipStreamSynchronize(o->stream));  // (a queued log launch may still write the old arrays)
+  if (o->d_log) HIPCHK(hipFree(o->d_log));
+  if (o->d_log_n) HIPCHK(hipFree(o->d_log_n));
+  o->d_log = nullptr;
+  o->d_log_n = nullptr;
+  o->log_cap = 0;
+  if (capacity == 0) return 0;
+  HIPCHK(hipMalloc((void **)&o->d_log, sizeof(agx_iter_record) * (size_t)o->B * capacity));
+  HIPCHK(hipMalloc((void **)&o->d_log_n, sizeof(int) * (size_t)o->B));
+  HIPCHK(hipMemsetAsync(o->d_log, 0, sizeof(agx_iter_record) * (size_t)o->B * capacity, o->stream));
+  HIPCHK(hipMemsetAsync(o->d_log_n, 0, sizeof(int) * (size_t)o->B, o->stream));
+  o->log_cap = capacity;
+  return 0;
+}
+
+int agx_ocp_iter_log_read(agx_ocp *o, agx_iter_record *out, int32_t *n) {
+  if (!o) return fail("null handle");
+  if (o->log_cap <= 0) return fail("agx_ocp_iter_log_read: the log is off (agx_ocp_iter_log)");
+  if (set_device(o)) return -1;
+  if (out) HIPCHK(hipMemcpyAsync(out, o->d_log, sizeof(agx_iter_record) * (size_t)o->B * o->log_cap, hipMemcpyDeviceToHost, o->stream));
+  if (n) HIPCHK(hipMemcpyAsync(n, o->d_log_n, sizeof(int) * (size_t)o->B, hipMemcpyDeviceToHost, o->stream));
+  HIPCHK(hipStreamSynchronize(o->stream));
+  return 0;
+}
+
+// Every cost item of every node on its own, at the resident (xs, us) with the references the solver would read (o->rv).  Reads
+// only: the iterate, the tiles, the solver state and the tile carry are left as they are (a staging buffer of its own).
+int agx_ocp_item_costs(agx_ocp *o, double *cost_r, double *Lx_r, double *Lu_r, double *cost_t, double *Lx_t) {
+  if (!o) return fail("null handle");
+  if (set_device(o)) return -1;
+  const int B = o->B, T = o->T, NV = o->nv, NX = o->nx, NU = o->nu, nvu = o->nvu;
+  const int Rr = o->n_rows_all[0], Rt = o->n_rows_all[1], R = std::max(std::max(Rr, Rt), 1);
+  const size_t units = (size_t)B * (T + 1) * R, total = units * (1 + NX + NU);
+  if (sizeof(double) * total > o->items_bytes) {
+    if (o->d_items) { HIPCHK(hipStreamSynchronize(o->stream)); HIPCHK(hipFree(o->d_items)); }
+    o->d_items = nullptr;
+    o->items_bytes = 0;
+    HIPCHK(hipMalloc((void **)&o->d_items, sizeof(double) * total));
+    o->items_bytes = sizeof(double) * total;
+  }
+  double *d_cost = o->d_items, *d_Lx = d_cost + units, *d_Lu = d_Lx + units * NX;
+  HIPCHK(hipMemsetAsync(o->d_items, 0, sizeof(double) * total, o->stream));  // inactive rows, rows a node type lacks, the terminal Lu
+  const DevRows *rows2 = (const DevRows *)((const char *)o->d_ocp + offsetof(DevOcp, rows));
+  const int rc = agx_diag_item_costs_launch((void *)o->stream, NV, o->chain ? 1 : 0, o->d_model, rows2, B, T, o->d_xs, o->d_us, &o->rv, R, d_cost, d_Lx,
+                                            d_Lu, o->obs_set ? o->d_obs : nullptr);
+  if (rc < 0) return fail("agx_ocp_item_costs: no kernel instantiation for nv = " + std::to_string(NV));
+  HIPCHK((hipError_t)rc);
+  if (o->cost_wide)  // the pair rows of a wide cost set: each pair's own value and gradient row
+    HIPCHK((hipError_t)agx_cost_pairs_launch(agx::kPairsItems, (void *)o->stream, (long long)B * (T + 1), o->d_model, o->d_ocp, o->d_cw, o->d_dt, o->d_xs,
+                                             &o->rv, d_cost, d_Lx, nullptr, 0, 0, R, o->obs_set ? o->d_obs : nullptr));
+  std::vector<double> h(total);
+  HIPCHK(hipMemcpyAsync(h.data(), o->d_items, sizeof(double) * total, hipMemcpyDeviceToHost, o->stream));
+  HIPCHK(hipStreamSynchronize(o->stream));
+  const double *h_cost = h.data(), *h_Lx = h_cost + units, *h_Lu = h_Lx + units * NX;
+  const int nxu = 2 * nvu;
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t <= T; ++t) {
+      const bool term = t == T;
+      const int Rn = term ? Rt : Rr;
+      double *c_out = term ? cost_t : cost_r, *x_out = term ? Lx_t : Lx_r;
+      const size_t node_out = term ? (size_t)b : (size_t)b * T + t;
+      for (int r = 0; r < Rn; ++r) {
+        const size_t u = ((size_t)b * (T + 1) + t) * R + r, w = node_out * Rn + r;
+        if (c_out) c_out[w] = h_cost[u];
+        if (x_out)
+          for (int i = 0; i < nvu; ++i) { x_out[w * nxu + i] = h_Lx[u * NX + i]; x_out[w * nxu + nvu + i] = h_Lx[u * NX + NV + i]; }
+        if (!term && Lu_r)
+          for (int i = 0; i < nvu; ++i) Lu_r[w * nvu + i] = h_Lu[u * NU + i];
+      }
+    }
   return 0;
 }
 
@@ -3145,6 +3254,7 @@ int agx_ocp_mpc_step(agx_ocp *o, int k0, int max_iter, int first) {
     }
   }
   if (solve_resident(o, max_iter, 0.0, prologue_done, carry_mode)) return -1;
+  (carry_mode != 0 ? o->steps_carried : o->steps_full) += 1;
   o->carry_armed = o->carry_static;
   o->carry_k0 = k0;
   return 0;

@@ -20,6 +20,7 @@ int agx_cost_pairs_launch(int dest, void *stream, long long nodes, const DevMode
     };
     if (dest == agx::kPairsToQp) to(std::integral_constant<int, agx::kPairsToQp>());
     else if (dest == agx::kPairsToCanonical) to(std::integral_constant<int, agx::kPairsToCanonical>());
+    else if (dest == agx::kPairsItems) to(std::integral_constant<int, agx::kPairsItems>());
     else to(std::integral_constant<int, agx::kPairsDistance>());
   };
   if (obs) launch((const agx::ObstaclePlacements *)obs); else launch();

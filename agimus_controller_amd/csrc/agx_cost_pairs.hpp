@@ -27,6 +27,9 @@ namespace agx {
 //   (k1_node_active) so that a tile K1 rewrote is added to once and a tile K1 kept is left alone.
 // DEST kPairsToCanonical: into Lx[q], Lxx[qq] and cost of the canonical tile (agx_ocp_calc_diff); `st` may be null.
 // DEST kPairsDistance: the distance of pair `which` at the running nodes, out [B][T] (agx_ocp_get_residuals).
+// DEST kPairsItems: every pair on its own (agx_ocp_item_costs): the lane that evaluates pair p stores its value w a(d) into
+//   out [B][T+1][which] and its gradient row w a'(d) g into the q half of auxs [B][T+1][which][2 NV] at row `first + p` of the
+//   caller's table (which: rows per node of those arrays), unscaled; no butterfly, nothing is summed.  `st` may be null.
 // sel: 0 every node, 1 running nodes, 2 terminal nodes.
 // OBS: empty, or ObstaclePlacements with one more argument (agx_ocp_set_obstacle_placements): a world-fixed geometry listed in
 // the table is placed at the pose of the node's instance, a per-lane load in place of the model's entry.
@@ -161,6 +164,15 @@ __global__ void __launch_bounds__(64) k_cost_pairs(const DevModel *__restrict__ 
     double a, ar, arr;
     activation1(P.act[pi], P.alpha[pi], aw0, d, a, ar, arr);
     cost += wi * a;
+    if constexpr (DEST == kPairsItems) {
+      if (act) {
+        const long long row = node * which + P.first + pi;
+        out[row] = wi * a;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) auxs[row * NX + i] = wi * ar * grow[i];
+      }
+      continue;
+    }
     const double c1 = wi * ar, c2 = wi * arr;
     int h = 0;
 #pragma unroll
@@ -171,7 +183,7 @@ __global__ void __launch_bounds__(64) k_cost_pairs(const DevModel *__restrict__ 
       for (int k = i; k < NV; ++k) H[h++] += cg * grow[k];
     }
   }
-  if constexpr (DEST == kPairsDistance) return;
+  if constexpr (DEST == kPairsDistance || DEST == kPairsItems) return;
   // ---- 8-lane butterfly: every lane ends with the node's cost and column l8 of Lq / Lqq
   const double sc = term ? 1.0 : dts[term ? 0 : t];
   cost += dpp_xor4(cost); cost += dpp_xor2(cost); cost += dpp_xor1(cost);

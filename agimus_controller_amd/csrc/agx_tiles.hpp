@@ -64,7 +64,7 @@ __device__ __forceinline__ const int *frames_at(const RefView &rv, int b, int t,
 
 namespace agx {
 
-constexpr int kPairsToQp = 0, kPairsToCanonical = 1, kPairsDistance = 2;  // destinations of k_cost_pairs (agx_cost_pairs.hpp)
+constexpr int kPairsToQp = 0, kPairsToCanonical = 1, kPairsDistance = 2, kPairsItems = 3;  // destinations of k_cost_pairs (agx_cost_pairs.hpp)
 
 template <int NV>
 struct QT {

@@ -640,6 +640,43 @@ class ShootingProblem:
         self.terminal_model = create_croco_dataclasses(self.terminal_model)
 
 
+# ------------------------------------------------------------------------ per-item costs
+@dataclasses.dataclass
+class CostItems:
+    """Every cost item of every node on its own, shaped like the arrays `_evaluate_ocp` of the MPC debugger fills
+    (agimus_controller_ros/mpc_debugger_node.py:241-323): `names` the union of running and terminal item names in first-seen node
+    order, `values` [n_names][T+1] weight * cost (NaN where a node type lacks the item), `jacobian` [n_names][(T+1)(nx+nu)]
+    weight * Lx | weight * Lu node after node (zero where a node type lacks the item; the terminal node has no control: its Lu
+    block is zero).  Differential level, as the debugger reads it: no factor dt."""
+
+    names: list[str]
+    values: np.ndarray
+    jacobian: np.ndarray
+
+
+def assemble_cost_items(running_names: T.Sequence[str], terminal_names: T.Sequence[str], items: T.Dict[str, np.ndarray], instance: int = 0) -> CostItems:
+    """`HipOcp.item_costs()` of one instance -> CostItems.  Row r of the running / terminal arrays is item r of that node type."""
+    cost_r, Lx_r, Lu_r, cost_t, Lx_t = (np.asarray(items[k])[instance] for k in ("cost_r", "Lx_r", "Lu_r", "cost_t", "Lx_t"))
+    T_, nx, nu = cost_r.shape[0], Lx_r.shape[-1], Lu_r.shape[-1]
+    assert cost_r.shape[1] == len(running_names) and cost_t.shape[0] == len(terminal_names)
+    names: list[str] = []
+    for name in list(running_names) + list(terminal_names):
+        if name not in names:
+            names.append(name)
+    values = np.full((len(names), T_ + 1), np.nan)
+    jac = np.zeros((len(names), T_ + 1, nx + nu))
+    for r, name in enumerate(running_names):
+        i = names.index(name)
+        values[i, :T_] = cost_r[:, r]
+        jac[i, :T_, :nx] = Lx_r[:, r]
+        jac[i, :T_, nx:] = Lu_r[:, r]
+    for r, name in enumerate(terminal_names):
+        i = names.index(name)
+        values[i, T_] = cost_t[r]
+        jac[i, T_, :nx] = Lx_t[r]
+    return CostItems(names=names, values=values, jacobian=jac.reshape(len(names), -1))
+
+
 # ------------------------------------------------------------------------ the OCP
 class OCPCrocoGeneric(OCPBaseCroco):
     def __init__(self, robot_models: RobotModels, params: OCPParamsBaseCroco, yaml_file: T.Union[str, T.IO],
@@ -766,6 +803,16 @@ class OCPCrocoGeneric(OCPBaseCroco):
             self._debug_data.references[idx] = (name, value)
         for idx, (name, _) in enumerate(self._debug_data.residuals):
             self._debug_data.residuals[idx] = (name, self._hip.residuals(names.index(name))[0])
+
+    def cost_items(self, states, controls) -> CostItems:
+        """Value and gradient of every cost item at every node of the trajectory (states [T+1][nx], controls [T][nu]) with the
+        references last set: what the MPC debugger reads out of Crocoddyl's cost data after problem.calc / calcDiff
+        (mpc_debugger_node.py:296-323).  The trajectory becomes the resident iterate of the handle, as a warm start would."""
+        T_ = self.n_controls
+        xs = np.asarray(states, dtype=np.float64).reshape(1, T_ + 1, self._nx)
+        us = np.asarray(controls, dtype=np.float64).reshape(1, T_, self._nv)
+        self._hip.upload_warmstart(xs, us)
+        return assemble_cost_items([i.name for i in self._items(False)], [i.name for i in self._items(True)], self._hip.item_costs())
 
     @staticmethod
     def get_default_yaml_file(basename: str) -> pathlib.Path:

@@ -19,6 +19,7 @@ from .factory.robot_model import RobotModels
 from .mpc_data import OCPDebugData, OCPResults
 from .ocp_base import OCPBase
 from .ocp_param_base import OCPParamsBaseCroco
+from .solver_log import SolverLog
 
 
 class OCPBaseCroco(OCPBase):
@@ -54,6 +55,12 @@ class OCPBaseCroco(OCPBase):
         self._ref_tile = self._packed.new_ref_tile(1)
         self._frames = self._packed.default_frames(1)
         self._last_status = None
+        # ocp_params.callbacks (reference ocp_base_croco.py:77-80: mim_solvers.CallbackVerbose + CallbackLogger): the solver
+        # keeps one record per SQP iteration on the device -- room for every iteration the solve may run: solver_iters, or 1000
+        # for use_iteration_limits_and_timeout=False -- and `solve` reads them into `solver_log` and prints the table AFTER the
+        # solve; upstream's callback prints each line as the solve runs.
+        self._solver_log: SolverLog | None = None
+        self._log_capacity = 0
 
     # -- the reference's properties ------------------------------------------
     @property
@@ -111,8 +118,14 @@ class OCPBaseCroco(OCPBase):
             max_time = float(self._ocp_params.max_solve_time)
         xs_ws = np.asarray(x_warmstart, dtype=np.float64).reshape(1, T + 1, self._nx)
         us_ws = np.asarray(u_warmstart, dtype=np.float64).reshape(1, T, self._nv)
+        if self._ocp_params.callbacks and self._log_capacity != max(int(max_iters), 1):
+            self._log_capacity = max(int(max_iters), 1)
+            self._hip.iter_log(self._log_capacity)
         xs, us, K, st = self._hip.solve(np.asarray(x0, dtype=np.float64).reshape(1, self._nx), xs_ws, us_ws, max_iters, max_time)
         self._last_status = st
+        if self._ocp_params.callbacks:
+            self._solver_log = SolverLog.from_records(*self._hip.read_iter_log())
+            print(self._solver_log.format(0))
         # lists of writable per-node arrays: the warm start mutates them in place
         # (warm_start_shift_previous_solution.py:95-104)
         ocp_results = OCPResults(
@@ -134,6 +147,11 @@ class OCPBaseCroco(OCPBase):
     @ocp_results.setter
     def ocp_results(self, value: OCPResults) -> None:
         self._ocp_results = value
+
+    @property
+    def solver_log(self) -> SolverLog | None:
+        """The per-iteration log of the last `solve` (ocp_params.callbacks), None without callbacks or before the first solve."""
+        return self._solver_log
 
     @property
     def debug_data(self) -> OCPDebugData:

@@ -171,6 +171,21 @@ typedef struct agx_status {
   int32_t flags;    /* bit0: non-finite result / discarded direction, bit1: a line search failed (all ten step lengths), bit2: a step length was rejected (the search backtracked) */
 } agx_status;
 
+/* One SQP iteration of one instance, as the per-iteration solver log keeps it (agx_ocp_iter_log): the line mim_solvers'
+ * CallbackVerbose prints per iteration (ocp_base_croco.py:77-80) minus ||(dx,du)||, which is not kept on the device, plus what
+ * only this solver knows: the regularisation, discarded directions and rejected step lengths.                              */
+typedef struct agx_iter_record {      /* 80 bytes */
+  double kkt, cost, merit, gap_norm, constraint_norm; /* evaluation at the start of the iteration:
+                                         what agx_status reports if the solve ends here */
+  double step;        /* accepted step length 2^-n; 0 = the iteration took no step */
+  double preg, dreg;  /* regularisation this iteration's direction was computed with */
+  int32_t iter, qp_iters, trials, flags;
+  /* trials: step lengths tried (1 .. 10; 0: no search).
+     flags bit0: converged in this iteration; bit1: direction discarded (failed factorisation);
+     bit2: all ten step lengths rejected; bit3: ended by cap / time limit / quorum before a search (the SQP loop as it stands
+     finishes the search of every iteration it starts, so the bit is never set at present) */
+} agx_iter_record;
+
 /* Doubles per node in the derivative tile written by the node-parallel pass:
  * Fx ndx^2 | Fu ndx*nu | f ndx | Lx ndx | Lu nu | Lxx ndx^2 | Lxu ndx*nu | Luu nu^2 | cost 1 */
 #define AGX_TILE_DOUBLES(nv) (4 * (nv) * (nv) + 2 * (nv) * (nv) + 2 * (nv) + 2 * (nv) + (nv) + 4 * (nv) * (nv) + 2 * (nv) * (nv) + (nv) * (nv) + 1)
@@ -287,6 +302,10 @@ int agx_ocp_first_pack_counts(agx_ocp *ocp, long long *served_in_solve, long lon
  * head of the step, without waiting for the queued trial round (batches above 204), and the number of instances whose derivative
  * tiles the next agx_ocp_mpc_step may inherit as the last solve published it (-1: not known).  Either pointer may be NULL.       */
 int agx_ocp_handoff_counts(agx_ocp *ocp, long long *early_exits, int *n_carriable);
+/* Introspection of the tile carry (tests): agx_ocp_mpc_step calls of this handle whose first derivative pass inherited the tiles
+ * of the previous step (some or all instances: nodes 0, T - 1 and T only for those) and calls that ran the full pass.  A carried
+ * and a full step hand out the same bits, so this is the only place the difference shows.  Either pointer may be NULL.         */
+int agx_ocp_carry_counts(agx_ocp *ocp, long long *steps_carried, long long *steps_full);
 
 /* Replaces WarmStartShiftPreviousSolution.shift
  * (warm_start_shift_previous_solution.py:85-109) on the resident solution.     */
@@ -325,6 +344,38 @@ int agx_model_sensitivity(agx_ocp *ocp, int n, double dt, const double *x, const
  * (ocp_croco_generic.py:840-853): residual of running row `row` at the resident
  * solution, out [B][T][nr] (a collision row, the pair rows of a wide cost set included: the distance). */
 int agx_ocp_get_residuals(agx_ocp *ocp, int row, double *out);
+
+/* ---- diagnostics -------------------------------------------------------- */
+/* Per-iteration solver log, the counterpart of OCPParamsBaseCroco.callbacks (mim_solvers.CallbackVerbose / CallbackLogger,
+ * ocp_base_croco.py:77-80).  agx_ocp_iter_log keeps room for `capacity` records per instance on the device (0 = off, the
+ * default: a solve then launches exactly the kernels of a handle that never had a log); the call waits for the solver stream.
+ * While on, every solving entry point (agx_ocp_solve, agx_ocp_solve_resident, agx_ocp_mpc_step) starts the log afresh and a
+ * small kernel copies the record of SQP iteration j of instance b to out[b][j], behind the head of the iteration (evaluation,
+ * regularisation) and behind its trial rounds (step, trials); the step kernels and the solver state are the same with the log
+ * on or off, and so is every result.  n[b] counts the iterations instance b started: status.iter + 1 for an instance that
+ * converged (the converging iteration has a record with step = 0 and flags bit0), status.iter otherwise (iteration cap,
+ * max_time, quorum cut, saturated regularisation).  Records beyond `capacity` are dropped, n[b] still counts them.
+ * agx_ocp_iter_log_read waits for the solver stream; out [B][capacity] (records j >= n[b] are stale or zero), n [B]; either
+ * may be NULL.  Every model capacity, constrained problems, both sweep flavours.                                           */
+int agx_ocp_iter_log(agx_ocp *ocp, int capacity);
+int agx_ocp_iter_log_read(agx_ocp *ocp, agx_iter_record *out, int32_t *n);
+/* What the MPC debugger reads out of Crocoddyl's data for every node and cost item (agimus_controller_ros
+ * mpc_debugger_node.py:241-323: weight * cost, weight * Lx, weight * Lu), at the resident (xs, us) with the references the
+ * solver would read (the handle's one reference view, whichever call set it: host tile, device tile, a window of a resident or
+ * streamed trajectory), the frame-id table and per-instance obstacle placements (per-instance model inertials enter no cost row
+ * a handle with them accepts):
+ *   cost_r [B][T][Rr], Lx_r [B][T][Rr][nx], Lu_r [B][T][Rr][nu], cost_t [B][Rt], Lx_t [B][Rt][nx]   (any may be NULL)
+ * with Rr / Rt ALL rows of the running / terminal table, the pair rows of a wide cost set included.  Values at the
+ * differential level, as the debugger shows them: item weight x a(r) and item weight x R' a'(r) WITHOUT the Euler factor dt
+ * (item x dt[t] summed over the items of a running node is the node's share in agx_ocp_calc_diff); the item weight is the
+ * first entry of the row in that node's reference tile.  An inactive row gives zeros, and so does a Control / ControlGrav row
+ * at the terminal node.  Gradients in the caller's joint layout [q | v].  Every row kind the handle accepts.
+ * The call only reads: the iterate, the solver state, the multipliers and the tile carry of agx_ocp_mpc_step are untouched.
+ * Kernels: k_item_costs (a lane per node and row), k_cost_pairs with the per-pair destination.  It waits for the solver stream.
+ * A set-up-class call: it stages B (T + 1) R (1 + nx + nu) doubles at the capacity sizes (R: the larger row count of the two
+ * node types) in a device buffer the handle keeps (grown on demand, never shrunk) and in a host buffer of the same size for the
+ * duration of the call -- several hundred MB at a batch of 1024 with a wide cost set; probe a few instances' worth of batch.   */
+int agx_ocp_item_costs(agx_ocp *ocp, double *cost_r, double *Lx_r, double *Lu_r, double *cost_t, double *Lx_t);
 
 /* ---- kernel-level entry points (parity tests and bench instrumentation) - */
 /* Node-parallel derivative pass at the resident (xs, us): writes the tiles to

@@ -15,5 +15,5 @@ PY
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -Iinclude $FLAGS "$@" -o build/obj/dev_g$G.o agimus_controller_amd/csrc/agimus_hip.hip
 OBJS=""
 for g in 0 1; do if [ $g = $G ]; then OBJS="$OBJS build/obj/dev_g$g.o"; else OBJS="$OBJS build/obj/agx_g$g.o"; fi; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/lib_dev.so $OBJS build/obj/agx_front.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/lib_dev.so $OBJS build/obj/agx_cost_pairs.o build/obj/agx_diag.o build/obj/agx_front.o
 echo built build/lib_dev.so

@@ -14,6 +14,7 @@ ap.add_argument("--horizon", type=int, default=100)
 ap.add_argument("--steps", type=int, default=200)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--max-iter", type=int, default=10)
+ap.add_argument("--iter-log", type=int, default=0, help="capacity of the per-iteration solver log (HipOcp.iter_log); 0: off")
 a = ap.parse_args()
 T, B, dt = a.horizon, a.batch, 0.01
 table = rt.panda_table(0.1)
@@ -24,6 +25,8 @@ h = backend.HipOcp(table, po, B)
 p = workloads.sine_batch_params(B, lower=table.lower_position_limit, upper=table.upper_position_limit)
 w = workloads.SINE_WEIGHTS
 h.sine_trajectory(a.warmup + a.steps + T + 2, dt, *p, w["w_q"], w["w_qdot"], w["w_effort"], w["w_pose"], tcp)
+if a.iter_log:
+    h.iter_log(a.iter_log)
 for k in range(a.warmup):
     h.mpc_step(k, a.max_iter, first=(k == 0))
     h.download_first(copy=False)
@@ -36,6 +39,6 @@ for k in range(a.warmup, a.warmup + a.steps):
     lat.append((time.perf_counter() - t1) * 1e3)
     its.append(float(st["iter"].mean()))
 lat = np.sort(np.array(lat))
-print(f"batch {B} T {T}: median {np.median(lat):.4f} ms  mean {lat.mean():.4f}  p99 {lat[int(0.99 * (len(lat) - 1))]:.4f}  "
+print(f"batch {B} T {T} iter-log {a.iter_log}: median {np.median(lat):.4f} ms  mean {lat.mean():.4f}  p99 {lat[int(0.99 * (len(lat) - 1))]:.4f}  "
       f"steps/s {B * 1e3 / lat.mean():.1f}  mean iters {np.mean(its):.2f}")
 h.close()
