@@ -30,307 +30,9 @@ extern "C" int agx_diag_iter_log_launch(void *stream, const DevState *st, int B,
 extern "C" int agx_diag_item_costs_launch(void *stream, int nv, int chain, const DevModel *m, const DevRows *rows2, int B, int T, const double *xs,
                                           const double *us, const RefView *rv, int R, double *cost, double *Lx, double *Lu, const void *obs);
 
-namespace {
-
-thread_local std::string g_err;
-int fail(const std::string &msg) {
-  g_err = msg;
-  return -1;
-}
-#define HIPCHK(expr)                                                                                      \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                \
-  } while (0)
-
-}  // namespace
-
-struct agx_model {
-  DevModel h;   // padded to the compiled capacity (see pad_capacity)
-  int nvu = 0;  // joints of the caller's model
-};
-
-struct agx_ocp {
-  DevModel hm;
-  DevOcp ho;
-  int nv = 0, nx = 0, nu = 0, T = 0, B = 0, tile = 0, stride = 0, device = 0;
-  // Model sizes at run time: the kernels exist for a few CAPACITIES (7 joints: eight lanes per node; 30 / 32: a workgroup per
-  // node).  A model with fewer joints is padded with massless, unit-armature joints that couple to nothing (pad_model): every
-  // cross term with a real joint is an exact zero, the pad block of each QP is an independent problem with zero data, so the
-  // real entries of xs, us, K, the costs and KKT residuals are what the exact-size recursion gives.  nv / nx / nu / stride above
-  // are the internal (capacity) sizes; nvu / stride_u the caller's.  Arrays crossing the C ABI are repacked on the host.
-  int nvu = 0, stride_u = 0;
-  bool padded = false;
-  std::vector<int> refmap[2];        // internal reference-tile element -> element of the caller's tile (-1: pad), running / terminal layout
-  std::vector<double> reffill[2];    // value of the pad elements
-  std::vector<double> stage;         // host staging of repacked arrays
-  std::vector<double> h_first_u;     // first-node results in the caller's layout
-  bool chain = false;
-  std::vector<double> dt;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  // device buffers
-  DevModel *d_model = nullptr;
-  DevOcp *d_ocp = nullptr;
-  double *d_dt = nullptr, *d_xs = nullptr, *d_us = nullptr, *d_x0 = nullptr, *d_tiles = nullptr;
-  double *d_Kws = nullptr, *d_kws = nullptr, *d_Kout = nullptr, *d_dx = nullptr, *d_du = nullptr;
-  double *d_Kws_lqr = nullptr, *d_kws_lqr = nullptr;  // gains of the plain LQR pass when it runs next to the ADMM factorisation
-  bool admm_prefactor = true;  // AGX_ADMM_PREFACTOR=0: LQR pass, then the factorisation inside the first ADMM iteration
-  double *d_qt = nullptr, *d_aux = nullptr, *d_w = nullptr, *d_nodestat = nullptr;  // QP tiles, aux tiles, acceleration steps
-  // constrained problems (agx_admm.hpp): augmented tiles, constraint values / collision Jacobians,
-  // multipliers y (persistent across solves), slack z, prox centre, per-node residual norms
-  bool has_con = false;
-  std::vector<int> shift_nodes;  // large models: nodes with dt_i != dt_0 (integrated by the warm-start shift)
-  int *d_shift_nodes = nullptr;
-  bool general = false;       // ControlGrav / FrameVelocity cost rows: one-lane GEN kernels (agx_general.hpp)
-  double *d_auxg = nullptr;   // [B][T+1][3 nv 8]: Lqv | Lvvd | Lqu of every node (general problems)
-  double *d_qt2 = nullptr, *d_cg = nullptr, *d_cjac = nullptr, *d_y = nullptr, *d_z = nullptr, *d_cx = nullptr, *d_admmstat = nullptr,
-         *d_fac = nullptr,  // Riccati factors of every node for the gradient-only ADMM sweeps [B][T][192]
-         *d_segP = nullptr;  // closed-loop transition products of the horizon segments [B][kSeg][4][64] (agx_admm.hpp)
-  bool admm_segments = true;  // AGX_ADMM_SEGMENTS=0: gradient-only sweeps on one wave per instance
-  int qt_size = 0, aux_size = 0;
-  bool k1_lanes = true;  // AGX_K1_LANES=0 selects the one-lane-per-node derivative kernel
-  bool lanes_ok = true;  // problem fits the LDS staging of the 8-lanes-per-node kernel
-  bool lanes_coll = false;  // ... in its variant with one collision cost row
-  // Wide cost set (agx_cost_pairs.hpp): ho.rows hold the non-collision prefix of the caller's row tables, the trailing collision
-  // rows live in hw (k_cost_pairs adds them to the tiles behind every K1 launch).  K1 reads d_ocp_k1, a copy of the description
-  // whose `stride` is the length of the prefix (what it stages in LDS); everybody else d_ocp with the stride of the tile.
-  bool cost_wide = false;
-  DevCostWide hw{};
-  DevCostWide *d_cw = nullptr;
-  DevOcp *d_ocp_k1 = nullptr;  // == d_ocp unless cost_wide
-  int n_rows_all[2] = {0, 0};  // rows of the caller's tables, running / terminal (ho.rows[l].n + hw.lay[l].n)
-  bool speculate = true;  // AGX_SPECULATE_GAINS=0: gains sweep only on exit
-  bool gains_mfma = true; // AGX_GAINS_MFMA=0: scalar K = M Kw - taux for large models
-  bool riccati_mx = true;    // AGX_RICCATI_MX=0: nv <= 7 sweeps on the 8 x 8 lane grid (k_riccati) instead of the MFMA operand layout (k_riccati_mx)
-  // Exact two-level sweep (agx_riccati_mx2.hpp): the horizon in mx2_S segments swept in parallel; 0 = the one-wave sweep.
-  // Chosen from the batch at creation (small batches leave most of the chip idle), AGX_MX2_SEGMENTS=n overrides (0: off).
-  int mx2_S = 0;
-  double *d_mx2_elem = nullptr, *d_mx2_bnd = nullptr, *d_mx2_cl = nullptr;  // [2][B][S][3][256] segment elements, [2][B][S][256] boundary value functions, [B][S][256] transitions under the gains
-  bool k1_fused = true;     // AGX_K1_FUSED=0: running and terminal nodes of the derivative pass as two launches (profiling)
-  bool node_kkt_wide = true;  // AGX_NODE_KKT_WIDE=0: nv <= 7 node shares by k_node_kkt (a wait per group of loads) instead of k_node_kkt_ahead
-  // Tile carry across MPC steps: the running-node tiles live in a ring (tile_slot, agx_kernels.hpp) whose
-  // origin advances with every carried agx_ocp_mpc_step, so that the first derivative pass of a step evaluates nodes 0, T - 1
-  // and T only.  7-joint capacity, eight-lane derivative kernel, unconstrained, MFMA-layout sweeps, one dt for every node.
-  bool tile_carry = true;       // AGX_TILE_CARRY=0: the full pass every step
-  bool carry_static = false;    // the problem qualifies (agx_ocp_create)
-  bool carry_armed = false;     // the last call that touched the iterate, the references or the tiles was an agx_ocp_mpc_step
-  int carry_k0 = 0;             // ... with this window
-  int head = 0;                 // DevOcp::head as the stream will see it
-  int n_carriable = -1;         // instances whose tiles the next step may inherit, as the last solve published it (-1: not known)
-  bool frames_uniform = true;   // the resident frame table holds one frame per row for every node (no per-node override uploaded)
-  // Batch policy (agx_ocp_set_quorum): the SQP loop of a batch step ends once this fraction of the instances has
-  // finished, the ADMM loop of an SQP iteration once this fraction of the QPs has converged; the others keep their
-  // iterate (solved = 0 / qp_iters = max_qp_iters) and continue from it at the next MPC step, as a lone controller
-  // that ran into max_solve_time would.  1.0 = wait for everyone (the default).
-  double quorum_sqp = 1.0, quorum_qp = 1.0;
-  bool con_lanes = true;          // constraint rows are control limits / state bounds / collision distances: k_con_eval_lj (AGX_CON_LANES=0: one lane per node)
-  bool con_wide = false;          // wide constraint set (DevCons: up to AGX_MAX_PAIRS collision pairs): k_con_eval_pairs, WIDE ADMM kernels (AGX_CON_WIDE=1 forces it where it applies)
-  int con_cs = AGX_MAX_NC;        // stride of g / y / z per node (wide sets: DevCons::cstride)
-  bool admm_loop_always = false;  // AGX_ADMM_LOOP=2 (tests): k_admm_loop whatever the number of unfinished instances
-  bool admm_loop = true;      // AGX_ADMM_LOOP=0: every ADMM iteration as three launches (sweep, update, reduce) instead of k_admm_loop
-  int n_unfinished = 1 << 30; // instances the SQP loop still works on (host's last count): k_admm_loop serves the tail of a step, when
-                              // few instances are left (with the whole batch active the node-parallel update across the chip is faster)
-  bool fold_publish = false;  // small batches (B <= 204, polled hand-off): the head / accept kernels hand the counters to the host themselves (last workgroup to arrive) and the host asks after the head from the second iteration on; AGX_FOLD_PUBLISH=0/1 overrides
-  int n_cu = 256;         // compute units of the device (grid of the persistent kernels)
-  bool no_empty = false;  // AGX_NO_EMPTY_LAUNCHES=1 (profiling): the host asks after the head of the step whether anybody searches and skips the trial launches otherwise, so that per-kernel averages are those of working launches
-  double *d_ref = nullptr;  // owned tile [B][T+1][stride]
-  // asynchronous reference upload (agx_ocp_set_refs_async): second tile / frame table filled by the copy stream while the
-  // solver works on the first; the next solve waits for the copy's event and swaps the two
-  double *d_ref_back = nullptr;
-  int *d_frames_back = nullptr;
-  bool refs_pending = false, refs_pending_frames = false;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_refs = nullptr, ev_snap = nullptr, ev_dl = nullptr;
-  // asynchronous result download (agx_ocp_download_async): device-side snapshot of xs | us | K taken in the solver's stream
-  double *d_snap = nullptr;
-  bool dl_pending = false;
-  int *d_frames = nullptr;  // owned [B][T+1][AGX_MAX_ROWS]
-  bool frames_set = false;
-  DevState *d_state = nullptr;
-  int *d_ndone = nullptr;
-  // pinned, fine-grained (coherent) mapped host words, 64 bit each: [0] finished-instance count, [1] its sequence
-  // stamp, [2] stamp of the packed results, [3] scratch value, [4] ADMM converged count, [5] its stamp, [6] / [7] line-search
-  // trials handed on / iterations ended with stale tiles, [8] instances with tiles the next MPC step may inherit, [9] instances
-  // whose first-node record k_sqp_head has packed, [10] stamp of the hand-off right behind the head of large batches and
-  // [11] / [12] / [13] its finished / inheritable / packed counts.
-  // Stamps are 64-bit and only ever grow (no wrap in practice); slots start at ~0, which no stamp takes.
-  unsigned long long *h_ndone = nullptr;
-  unsigned long long *h_ndone_dev = nullptr;  // the same words as the device sees them (mapped host memory)
-  unsigned long long seq = 0;
-  unsigned ls_handed = 0, ls_stale = 0;  // last values seen of the device counters of handed-on line-search trials / iterations ended with stale tiles (d_ndone[3], [4]; never reset)
-  bool poll = true;  // AGX_HOST_POLL=0: stream-ordered copies + synchronize instead of polled mapped words
-  double *d_first = nullptr, *h_first = nullptr;  // packed first-node results [B][first_stride], device / pinned host
-  int first_stride = 0;
-  // First-node records packed during the solve (k_sqp_head, agx_ocp_set_first_pack): once the block exists the head gets it, and
-  // a solve that every instance ended by packing its record leaves it fresh -- agx_ocp_first_packed then returns it as it is.
-  bool first_in_solve = true;
-  bool first_fresh = false;  // the block holds the results of the last solve and nothing has touched xs / us / K / the state since
-  int n_packed = 0;          // records packed in the running solve, as last published
-  long long first_served[2] = {0, 0};  // agx_ocp_first_packed calls served from the fresh block / by k_pack_first
-  long long steps_carried = 0, steps_full = 0;  // agx_ocp_mpc_step calls whose first derivative pass inherited tiles (carry_mode != 0) / ran in full (agx_ocp_carry_counts)
-  long long early_exits = 0;  // SQP loops that ended on the hand-off right behind the head, without waiting for the trial round (agx_ocp_handoff_counts)
-  double *d_scratch = nullptr;
-  size_t scratch_bytes = 0;
-  // plant of the closed loop (agx_ocp_set_plant_inertials): agx::PlantInertials<nv>[B], read by k_plant_rollout only
-  double *d_plant = nullptr;
-  bool plant_set = false;
-  std::vector<double> plant_stage;  // host image of d_plant (the upload reads it after the setter has returned the caller's arrays)
-  // per-instance controller model (agx_ocp_set_model_inertials, 7-joint capacity): agx::InstanceInertials<nv>[B].  While set,
-  // every launch that evaluates dynamics goes to the instantiation that reads it (with_sources), as does the plant-less rollout.
-  double *d_minert = nullptr;
-  bool minert_set = false;
-  std::vector<double> minert_stage;
-  // per-instance obstacle placements (agx_ocp_set_obstacle_placements, 7-joint capacity): one buffer, agx::ObstaclePlacements (the
-  // frame -> slot map) followed by se3 [B][n][12].  While set, every launch that evaluates a collision distance goes to the
-  // instantiation that reads it (with_sources); unset, nothing of a launch differs from a handle that never had a table.
-  void *d_obs = nullptr;
-  size_t obs_bytes = 0;  // allocated
-  bool obs_set = false;
-  std::vector<double> obs_stage;  // host image of d_obs
-  RefView rv{};
-  // resident trajectory
-  double *d_traj = nullptr, *d_pts = nullptr;
-  double *d_sine = nullptr;  // q0, amp, puls, scale, t0
-  int n_points = 0;
-  // non-uniform horizon indexes (TrajectoryBuffer): empty = node t looks at sample k0 + t
-  std::vector<int> hidx;
-  int *d_hidx = nullptr;
-  int win_logical = -1;  // streamed ring: logical start of the last window set (-1: none since the ring was created)
-  int win_k0 = 0;  // physical start sample of the window (a streamed ring: slot k0 mod capacity)
-  // Streamed resident trajectory (agx_traj_stream_*): d_traj / d_pts hold a ring of st_cap sample slots per
-  // instance followed by st_span - 1 mirror slots (n_points = their sum); logical samples [st_first, st_end) are retained,
-  // sample k in slot k mod st_cap.  An append stages its chunk in one of two page-locked buffers, copies it to the device twin and
-  // fills the slots on the copy stream; ev_st[i] is recorded behind the fill.  st_pending[i]: the solver stream has not been made
-  // to wait for that append yet (done when a window or a reader reaches a sample >= st_lo[i]).
-  bool streamed = false;
-  int st_cap = 0, st_span = 0, st_first = 0, st_end = 0;
-  int st_chunk = 0;  // samples per instance a staging buffer holds (longer appends go in pieces)
-  double *st_host[2] = {nullptr, nullptr}, *d_st_stage[2] = {nullptr, nullptr};
-  hipEvent_t ev_st[2] = {nullptr, nullptr}, ev_st_solver = nullptr;
-  bool st_used[2] = {false, false}, st_pending[2] = {false, false};
-  int st_lo[2] = {0, 0};
-  int st_next = 0;
-  // agx_traj_stream_timing: while on, every join is bracketed by two events on the solver stream ([0]: how long that stream sat
-  // waiting for a fill) and every appended piece by two on the copy stream ([1]: transfer + fill); pairs are kept until read
-  bool st_timing = false;
-  std::vector<hipEvent_t> st_tev[2];  // [kind][2 * k] start, [2 * k + 1] stop
-  size_t st_tev_used[2] = {0, 0};
-  double st_tms[2] = {0.0, 0.0};
-  long long st_tn[2] = {0, 0};
-  long long st_joins = 0;  // times the solver stream was made to wait for an append (agx_traj_stream_joins)
-  agx::SineParams st_sp{};  // weights and frame given at create
-  // the device work of the last appended piece (agx_ocp_time_kernel(10) repeats it): staging buffer, samples, logical start,
-  // doubles copied, kernel parameters
-  struct { int buf = -1, m = 0, end = 0; size_t used = 0; agx::SineParams sp{}; } st_last;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_done = nullptr;
-  int last_max_iter = 0;
-  // per-iteration solver log (agx_ocp_iter_log): records [B][log_cap] and counts [B] on the device; log_cap == 0: off, and a solve
-  // launches nothing for it
-  int log_cap = 0;
-  agx_iter_record *d_log = nullptr;
-  int *d_log_n = nullptr;
-  // staging of agx_ocp_item_costs (cost | Lx | Lu of every node and row at the capacity), grown on demand
-  double *d_items = nullptr;
-  size_t items_bytes = 0;
-  // in-situ kernel timing (agx_ocp_profile): event pairs around the launches of the SQP loop
-  bool prof = false;
-  std::vector<hipEvent_t> prof_ev;  // [2 * k] start, [2 * k + 1] stop
-  std::vector<int> prof_kind;
-  double prof_ms[3] = {0, 0, 0};
-  long long prof_n[3] = {0, 0, 0};
-};
+#include "agx_host_handle.hpp"
 
 namespace {
-
-int set_device(agx_ocp *o) {
-  HIPCHK(hipSetDevice(o->device));
-  return 0;
-}
-
-// capacity a model of nv joints runs at: the smallest compiled size that holds it (0: none)
-int pad_capacity(int nv);
-
-// ---- repacking between the caller's layout (nvu joints) and the internal one (nv = capacity) -----------------------------
-// rows of `blocks` blocks of nvu doubles  <->  rows of `blocks` blocks of nv doubles
-void pad_rows(double *dst, const double *src, size_t rows, int blocks, int nvu, int nv, double fill) {
-  for (size_t r = 0; r < rows; ++r)
-    for (int b = 0; b < blocks; ++b) {
-      double *d = dst + (r * blocks + b) * nv;
-      const double *q = src + (r * blocks + b) * nvu;
-      for (int i = 0; i < nvu; ++i) d[i] = q[i];
-      for (int i = nvu; i < nv; ++i) d[i] = fill;
-    }
-}
-void unpad_rows(double *dst, const double *src, size_t rows, int blocks, int nvu, int nv) {
-  for (size_t r = 0; r < rows; ++r)
-    for (int b = 0; b < blocks; ++b) {
-      double *d = dst + (r * blocks + b) * nvu;
-      const double *q = src + (r * blocks + b) * nv;
-      for (int i = 0; i < nvu; ++i) d[i] = q[i];
-    }
-}
-// host -> device of [rows][blocks][nvu] into [rows][blocks][nv]; synchronous for padded handles (staging is reused)
-int up(agx_ocp *o, double *d_dst, const double *h_src, size_t rows, int blocks, double fill = 0.0) {
-  if (!o->padded) {
-    HIPCHK(hipMemcpyAsync(d_dst, h_src, sizeof(double) * rows * blocks * o->nv, hipMemcpyHostToDevice, o->stream));
-    return 0;
-  }
-  o->stage.resize(rows * blocks * o->nv);
-  pad_rows(o->stage.data(), h_src, rows, blocks, o->nvu, o->nv, fill);
-  HIPCHK(hipMemcpyAsync(d_dst, o->stage.data(), sizeof(double) * o->stage.size(), hipMemcpyHostToDevice, o->stream));
-  HIPCHK(hipStreamSynchronize(o->stream));
-  return 0;
-}
-// device -> host of [rows][blocks][nv] into [rows][blocks][nvu]; padded handles synchronize inside
-int down(agx_ocp *o, double *h_dst, const double *d_src, size_t rows, int blocks) {
-  if (!o->padded) {
-    HIPCHK(hipMemcpyAsync(h_dst, d_src, sizeof(double) * rows * blocks * o->nv, hipMemcpyDeviceToHost, o->stream));
-    return 0;
-  }
-  o->stage.resize(rows * blocks * o->nv);
-  HIPCHK(hipMemcpyAsync(o->stage.data(), d_src, sizeof(double) * o->stage.size(), hipMemcpyDeviceToHost, o->stream));
-  HIPCHK(hipStreamSynchronize(o->stream));
-  unpad_rows(h_dst, o->stage.data(), rows, blocks, o->nvu, o->nv);
-  return 0;
-}
-// gains: [n][nv][2 nv] on the device -> [n][nvu][2 nvu]
-int down_gains(agx_ocp *o, double *h_dst, const double *d_src, size_t n) {
-  if (!o->padded) {
-    HIPCHK(hipMemcpyAsync(h_dst, d_src, sizeof(double) * n * o->nu * o->nx, hipMemcpyDeviceToHost, o->stream));
-    return 0;
-  }
-  const int nv = o->nv, nvu = o->nvu;
-  o->stage.resize(n * nv * 2 * nv);
-  HIPCHK(hipMemcpyAsync(o->stage.data(), d_src, sizeof(double) * o->stage.size(), hipMemcpyDeviceToHost, o->stream));
-  HIPCHK(hipStreamSynchronize(o->stream));
-  for (size_t r = 0; r < n; ++r)
-    for (int i = 0; i < nvu; ++i)
-      unpad_rows(h_dst + (r * nvu + i) * 2 * nvu, o->stage.data() + (r * nv + i) * 2 * nv, 1, 2, nvu, nv);
-  return 0;
-}
-// reference tile [nodes][stride_u] (running layout, `term_every` > 0: every term_every-th node in the terminal layout)
-void pad_ref_tile(const agx_ocp *o, double *dst, const double *src, size_t B, int T) {
-  for (size_t b = 0; b < B; ++b)
-    for (int t = 0; t <= T; ++t) {
-      const int lay = t == T ? 1 : 0;
-      const double *q = src + (b * (T + 1) + t) * o->stride_u;
-      double *d = dst + (b * (T + 1) + t) * o->stride;
-      const int *map = o->refmap[lay].data();
-      const double *fill = o->reffill[lay].data();
-      for (int e = 0; e < o->stride; ++e) d[e] = map[e] >= 0 ? q[map[e]] : fill[e];
-    }
-}
-
-int ensure_scratch(agx_ocp *o, size_t bytes) {
-  if (bytes <= o->scratch_bytes) return 0;
-  if (o->d_scratch) HIPCHK(hipFree(o->d_scratch));
-  o->d_scratch = nullptr;
-  o->scratch_bytes = 0;
-  HIPCHK(hipMalloc(&o->d_scratch, bytes));
-  o->scratch_bytes = bytes;
-  return 0;
-}
 
 void fill_rows(const agx_cost_row *rows, int n, int nv, int nvu, DevRows &d) {
   std::memset(&d, 0, sizeof(d));
@@ -507,6 +209,7 @@ int fill_cons_wide(const agx_constraint_row *rows, int n, int nv, int nvu, const
 #define AGX_FOR_NV(MACRO) MACRO(7) MACRO(16) MACRO(30) MACRO(32)
 #endif
 
+// capacity a model of nv joints runs at: the smallest compiled size that holds it (0: none)
 int pad_capacity(int nv) {
   int best = 0;
 #define AGX_CAP(N) if (N >= nv && (best == 0 || N < best)) best = N;
@@ -538,12 +241,6 @@ int dispatch(int nv, bool chain, F &&f) {
 #undef AGX_NAME
 }
 
-int ensure_canonical_tiles(agx_ocp *o) {
-  if (o->d_tiles) return 0;
-  HIPCHK(hipMalloc((void **)&o->d_tiles, sizeof(double) * (size_t)o->B * (o->T + 1) * o->tile));
-  return 0;
-}
-
 // Per-instance sources.  The 7-joint kernels that evaluate dynamics or a collision distance end in a template pack: empty,
 // InstanceInertials<NV> (agx_ocp_set_model_inertials), ObstaclePlacements (agx_ocp_set_obstacle_placements) or both in that order,
 // one more argument each (agx_device.hpp: pack_has, pack_ptr, world_of).  with_sources calls f(sources...) with the trailing
@@ -566,7 +263,7 @@ void with_sources(agx_ocp *o, F &&f) {
 }
 
 int launch_calc_diff_rows(agx_ocp *o, bool masked, bool running_only) {
-  if (ensure_canonical_tiles(o)) return -1;
+  if (!o->d_tiles) HIPCHK(o->own.device(&o->d_tiles, (size_t)o->B * (o->T + 1) * o->tile));  // the canonical tiles: on first use
   return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
     constexpr int NV = decltype(NVc)::value;
     constexpr bool CH = decltype(CHc)::value;
@@ -692,9 +389,9 @@ int launch_riccati(agx_ocp *o, int forward, bool pair = false, int iter = 0, con
       // small batches: segments in parallel, exact boundary value functions (agx_riccati_mx2.hpp)
       const int S = o->mx2_S, P2 = pair ? 2 : 1;
       if (!o->d_mx2_elem) {
-        HIPCHK(hipMalloc((void **)&o->d_mx2_elem, sizeof(double) * 2 * (size_t)o->B * S * 768));
-        HIPCHK(hipMalloc((void **)&o->d_mx2_bnd, sizeof(double) * 2 * (size_t)o->B * S * 256));
-        HIPCHK(hipMalloc((void **)&o->d_mx2_cl, sizeof(double) * (size_t)o->B * S * 256));
+        HIPCHK(o->own.device(&o->d_mx2_elem, 2 * (size_t)o->B * S * 768));
+        HIPCHK(o->own.device(&o->d_mx2_bnd, 2 * (size_t)o->B * S * 256));
+        HIPCHK(o->own.device(&o->d_mx2_cl, (size_t)o->B * S * 256));
       }
       hipLaunchKernelGGL((agx::k_riccati_mx2_elem<NV>), dim3(P2 * o->B * S), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_aux,
                          o->d_Kws, o->d_kws, o->d_Kout, o->d_state, o->d_mx2_elem, o->d_mx2_bnd, o->d_mx2_cl, S, pair ? 1 : 0, 0, 1, iter);
@@ -786,7 +483,7 @@ int launch_step(agx_ocp *o, int iter, int max_iter, int mode, bool with_node_kkt
 // gmode 0: every instance; 2: only instances whose last direction has no (speculative) sweep yet.
 int launch_gains(agx_ocp *o, int gmode = 0) {
   if (o->nv <= 7 && o->T + 1 > 512) return fail("the sweeps stage the step lengths of up to 511 nodes in LDS: horizon too long");
-  if (o->nv > 7 && !o->d_qt2) HIPCHK(hipMalloc((void **)&o->d_qt2, sizeof(double) * (size_t)o->B * (o->T + 1) * o->qt_size));
+  if (o->nv > 7 && !o->d_qt2) HIPCHK(o->own.device(&o->d_qt2, (size_t)o->B * (o->T + 1) * o->qt_size));
   return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
     constexpr int NV = decltype(NVc)::value;
     if constexpr (NV <= 7) {
@@ -846,15 +543,16 @@ int launch_rollout(agx_ocp *o, int n_substeps, double dt_sub, const double *d_di
 
 int prof_mark(agx_ocp *o, int kind, bool start) {
   if (!o->prof) return 0;
-  hipEvent_t e;
-  HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(e, o->stream));
-  o->prof_ev.push_back(e);
+  if (o->prof_used == o->prof_ev.size()) {  // events are created once and reused by every later solve
+    o->prof_ev.push_back(nullptr);
+    HIPCHK(o->own.event(&o->prof_ev.back()));
+  }
+  HIPCHK(hipEventRecord(o->prof_ev[o->prof_used++], o->stream));
   if (start) o->prof_kind.push_back(kind);
   return 0;
 }
 int prof_collect(agx_ocp *o) {
-  if (!o->prof || o->prof_ev.empty()) return 0;
+  if (!o->prof || o->prof_used == 0) return 0;
   HIPCHK(hipStreamSynchronize(o->stream));
   for (size_t k = 0; k < o->prof_kind.size(); ++k) {
     float ms = 0.f;
@@ -862,8 +560,7 @@ int prof_collect(agx_ocp *o) {
     o->prof_ms[o->prof_kind[k]] += ms;
     o->prof_n[o->prof_kind[k]] += 1;
   }
-  for (hipEvent_t e : o->prof_ev) (void)hipEventDestroy(e);
-  o->prof_ev.clear();
+  o->prof_used = 0;
   o->prof_kind.clear();
   return 0;
 }
@@ -943,8 +640,8 @@ int admm_direction_nv7(agx_ocp *o, bool prefactor) {
   const int g8 = (int)((nodes * 8 + 255) / 256), g8b = (int)((nodes * 8 + 127) / 128), g1 = (int)((nodes + 255) / 256);
   if (prefactor) {
     if (!o->d_Kws_lqr) {
-      HIPCHK(hipMalloc((void **)&o->d_Kws_lqr, sizeof(double) * (size_t)o->B * o->T * o->nu * o->nx));
-      HIPCHK(hipMalloc((void **)&o->d_kws_lqr, sizeof(double) * (size_t)o->B * o->T * o->nu));
+      HIPCHK(o->own.device(&o->d_Kws_lqr, (size_t)o->B * o->T * o->nu * o->nx));
+      HIPCHK(o->own.device(&o->d_kws_lqr, (size_t)o->B * o->T * o->nu));
     }
     // constraint data and the augmented Hessians need only (xs, us) and rho: before the LQR pass
     launch_con_eval<NV, CH>(o, o->d_xs, o->d_us, 0);
@@ -1111,79 +808,18 @@ int adopt_pending_refs(agx_ocp *o) {
   if (carry_invalidate(o)) return -1;
   if (o->refs_pending_frames) o->frames_uniform = false;
   HIPCHK(hipStreamWaitEvent(o->stream, o->ev_refs, 0));
-  std::swap(o->d_ref, o->d_ref_back);
+  std::swap(o->d_ref, o->d_ref_back);  // (both fields stay registered with the owner, which reads them when it frees)
   if (o->refs_pending_frames) std::swap(o->d_frames, o->d_frames_back);
-  o->rv.base = o->d_ref;
-  o->rv.bstride = (long long)(o->T + 1) * o->stride;
-  o->rv.tstride = o->stride;
-  o->rv.term_off = 0;
-  o->rv.frames = o->refs_pending_frames ? o->d_frames : nullptr;
+  rv_own_tile(o, o->refs_pending_frames ? o->d_frames : nullptr);
   o->refs_pending = false;
   return 0;
 }
 int ensure_copy_stream(agx_ocp *o) {
   if (o->copy_stream) return 0;
   HIPCHK(hipStreamCreateWithFlags(&o->copy_stream, hipStreamNonBlocking));
-  HIPCHK(hipEventCreateWithFlags(&o->ev_refs, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&o->ev_snap, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&o->ev_dl, hipEventDisableTiming));
-  return 0;
-}
-
-// The handle stops being a streamed ring (another trajectory is created, or a new ring): fills still queued on the copy stream
-// write d_traj / d_pts, so the host waits for them before those are freed.  The staging buffers go too: a new ring sizes its own.
-int stream_end(agx_ocp *o) {
-  if (!o->streamed) return 0;
-  HIPCHK(hipStreamSynchronize(o->copy_stream));
-  for (int i = 0; i < 2; ++i) {
-    if (o->d_st_stage[i]) { (void)hipFree(o->d_st_stage[i]); o->d_st_stage[i] = nullptr; }
-    if (o->st_host[i]) { (void)hipHostFree(o->st_host[i]); o->st_host[i] = nullptr; }
-    o->st_used[i] = o->st_pending[i] = false;
-  }
-  o->streamed = false;
-  o->st_last.buf = -1;
-  o->st_cap = o->st_span = o->st_first = o->st_end = o->st_chunk = 0;
-  return 0;
-}
-int stream_enqueue_last(agx_ocp *o, bool behind_solver);
-// next event of the timing pairs of `kind`, recorded on `s` (events are created once and reused after every read-out)
-int stream_time_mark(agx_ocp *o, int kind, hipStream_t s) {
-  if (!o->st_timing) return 0;
-  if (o->st_tev_used[kind] == o->st_tev[kind].size()) {
-    hipEvent_t e = nullptr;
-    HIPCHK(hipEventCreate(&e));
-    o->st_tev[kind].push_back(e);
-  }
-  HIPCHK(hipEventRecord(o->st_tev[kind][o->st_tev_used[kind]++], s));
-  return 0;
-}
-// The solver stream waits (the host does not) for every append not yet joined that wrote a sample below `upto`.
-int stream_join(agx_ocp *o, int upto) {
-  for (int n = 0; n < 2; ++n) {
-    const int i = (o->st_next + n) % 2;  // the older buffer first
-    if (o->st_pending[i] && o->st_lo[i] < upto) {
-      if (stream_time_mark(o, 0, o->stream)) return -1;
-      HIPCHK(hipStreamWaitEvent(o->stream, o->ev_st[i], 0));
-      if (stream_time_mark(o, 0, o->stream)) return -1;
-      o->st_pending[i] = false;
-      ++o->st_joins;
-    }
-  }
-  return 0;
-}
-// Sample index of a resident trajectory as the kernels and copies address it: `k` itself, or on a streamed ring the slot of
-// logical sample k, with the samples [k, k + span) required inside [first, end) and their appends joined.
-int traj_locate(agx_ocp *o, const char *fn, const char *what, int k, int span, int *phys) {
-  if (!o->streamed) {
-    if (k < 0 || (long long)k + span > o->n_points) return fail(std::string(fn) + ": " + what);
-    *phys = k;
-    return 0;
-  }
-  if (k < o->st_first || (long long)k + span > o->st_end)
-    return fail(std::string(fn) + ": samples [" + std::to_string(k) + ", " + std::to_string((long long)k + span) + ") are not inside the retained range [first, end) = [" +
-                std::to_string(o->st_first) + ", " + std::to_string(o->st_end) + ") of the streamed trajectory");
-  if (stream_join(o, k + span)) return -1;
-  *phys = k % o->st_cap;
+  HIPCHK(o->own.event(&o->ev_refs, hipEventDisableTiming));
+  HIPCHK(o->own.event(&o->ev_snap, hipEventDisableTiming));
+  HIPCHK(o->own.event(&o->ev_dl, hipEventDisableTiming));
   return 0;
 }
 
@@ -1401,6 +1037,8 @@ int launch_cost_pairs(agx_ocp *o, int dest, int sel, int phase, bool masked, int
 
 }  // namespace
 
+#include "agx_host_traj.hpp"
+
 extern "C" {
 
 const char *agx_last_error(void) { return g_err.c_str(); }
@@ -1576,6 +1214,12 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
     }
   }
   agx_ocp *o = new agx_ocp();
+  o->device = device;
+  // every failure from here on leaves through agx_ocp_destroy (`bail` with a message, or after a callee has set one)
+  auto bail = [o](const std::string &msg) {
+    agx_ocp_destroy(o);
+    return fail(msg);
+  };
   o->hm = m->h;
   o->nv = m->h.nv; o->nx = 2 * o->nv; o->nu = o->nv;
   o->chain = m->h.is_chain != 0;
@@ -1590,7 +1234,7 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   if (const char *e = getenv("AGX_K1_FUSED")) o->k1_fused = (e[0] != '0');
   if (const char *e = getenv("AGX_NODE_KKT_WIDE")) o->node_kkt_wide = (e[0] != '0');
   if (const char *e = getenv("AGX_TILE_CARRY")) o->tile_carry = (e[0] != '0');
-  o->T = d->horizon; o->B = batch; o->device = device;
+  o->T = d->horizon; o->B = batch;
   {
     int n = 0;
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0) o->n_cu = n;
@@ -1656,16 +1300,13 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
     if (const char *e = getenv("AGX_CON_WIDE")) wide = wide_ok && e[0] == '1';
     if (!wide && (fill_cons(d->running_constraints, d->n_running_constraints, o->nv, o->nvu, m->h, o->ho.cons[0], false) ||
                   fill_cons(d->terminal_constraints, d->n_terminal_constraints, o->nv, o->nvu, m->h, o->ho.cons[1], true))) {
-      if (wide_model && (wc_r == 2 || wc_t == 2)) {
-        delete o;
-        return fail("agx_ocp_create: at most " + std::to_string(AGX_MAX_PAIRS) + " collision-pair constraints per node type");
-      }
-      if (!wide_ok) { delete o; return -1; }
+      if (wide_model && (wc_r == 2 || wc_t == 2)) return bail("agx_ocp_create: at most " + std::to_string(AGX_MAX_PAIRS) + " collision-pair constraints per node type");
+      if (!wide_ok) { agx_ocp_destroy(o); return -1; }
       wide = true;
     }
     if (wide) {
       if (fill_cons_wide(d->running_constraints, d->n_running_constraints, o->nv, o->nvu, m->h, o->ho.cons[0], false) ||
-          fill_cons_wide(d->terminal_constraints, d->n_terminal_constraints, o->nv, o->nvu, m->h, o->ho.cons[1], true)) { delete o; return -1; }
+          fill_cons_wide(d->terminal_constraints, d->n_terminal_constraints, o->nv, o->nvu, m->h, o->ho.cons[1], true)) { agx_ocp_destroy(o); return -1; }
       const int cs = std::max(1, std::max(o->ho.cons[0].nc, o->ho.cons[1].nc)), js = std::max(1, std::max(o->ho.cons[0].npairs, o->ho.cons[1].npairs));
       for (int lay = 0; lay < 2; ++lay) { o->ho.cons[lay].cstride = cs; o->ho.cons[lay].jstride = js; }
       o->con_wide = o->ho.cons[0].nc + o->ho.cons[1].nc > 0;
@@ -1689,10 +1330,8 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   if (o->has_con && o->nv > 7) {  // large models: ConstraintModelControlLimit only (agx_big.hpp)
     for (int lay = 0; lay < 2; ++lay)
       for (int r = 0; r < o->ho.cons[lay].n; ++r)
-        if (o->ho.cons[lay].kind[r] == AGX_RES_FRAME_VELOCITY || o->ho.cons[lay].kind[r] == AGX_RES_CONTROL_GRAV) {
-          delete o;
-          return fail("agx_ocp_create: FrameVelocity / ControlGrav constraints are implemented for models of at most 7 joints (after padding)");
-        }
+        if (o->ho.cons[lay].kind[r] == AGX_RES_FRAME_VELOCITY || o->ho.cons[lay].kind[r] == AGX_RES_CONTROL_GRAV)
+          return bail("agx_ocp_create: FrameVelocity / ControlGrav constraints are implemented for models of at most 7 joints (after padding)");
   }
   {
     auto n_frame_rows = [](const DevRows &r) {
@@ -1730,8 +1369,8 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
           n += r.kind[i] == AGX_RES_FRAME_PLACEMENT ? 6 : ((r.kind[i] == AGX_RES_FRAME_TRANSLATION || r.kind[i] == AGX_RES_FRAME_ROTATION) ? 3 : (r.kind[i] == AGX_RES_COLLISION ? 1 : 0));
       return n;
     };
-    if (o->stride > agx::kWgRef) { delete o; return fail("agx_ocp_create: reference tile of " + std::to_string(o->stride) + " doubles per node exceeds the large-model limit of " + std::to_string(agx::kWgRef)); }
-    if (n_dense(o->ho.rows[0]) > agx::kWgJ || n_dense(o->ho.rows[1]) > agx::kWgJ) { delete o; return fail("agx_ocp_create: more than 16 frame / collision residual components per node (large models)"); }
+    if (o->stride > agx::kWgRef) return bail("agx_ocp_create: reference tile of " + std::to_string(o->stride) + " doubles per node exceeds the large-model limit of " + std::to_string(agx::kWgRef));
+    if (n_dense(o->ho.rows[0]) > agx::kWgJ || n_dense(o->ho.rows[1]) > agx::kWgJ) return bail("agx_ocp_create: more than 16 frame / collision residual components per node (large models)");
   }
   // two-level sweep for small batches of unconstrained problems on the MFMA-layout kernel.  Only with Gauss-Newton Hessians of
   // quadratic activations: then Hww = M (Luu + preg) M is positive definite at every node and no sweep -- neither the ordinary one
@@ -1761,95 +1400,77 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
                       !o->cost_wide;  // (a wide cost set does not carry tiles: k_cost_pairs adds to the tiles of the pass in front of it)
   }
   // probe that a kernel instantiation exists
-  if (dispatch(o->nv, o->chain, [](auto, auto) -> int { return 0; })) { delete o; return -1; }
-  if (set_device(o)) { delete o; return -1; }
+  if (dispatch(o->nv, o->chain, [](auto, auto) -> int { return 0; }) || set_device(o)) { agx_ocp_destroy(o); return -1; }
   const size_t B = o->B, T = o->T, nx = o->nx, nu = o->nu;
-#define ALLOC(ptr, count)                                                                                   \
-  do {                                                                                                      \
-    hipError_t e_ = hipMalloc((void **)&(ptr), sizeof(*(ptr)) * (count));                                  \
-    if (e_ != hipSuccess) { agx_ocp_destroy(o); return fail(std::string("hipMalloc " #ptr ": ") + hipGetErrorString(e_)); } \
-    (void)hipMemset((ptr), 0, sizeof(*(ptr)) * (count));                                                   \
-  } while (0)
-  ALLOC(o->d_model, 1);
-  ALLOC(o->d_ocp, o->cost_wide ? 2 : 1);  // wide cost sets: [1] the copy K1 reads
-  o->d_ocp_k1 = o->d_ocp;
-  if (o->cost_wide) ALLOC(o->d_cw, 1);
-  ALLOC(o->d_dt, T);
-  ALLOC(o->d_xs, 2 * B * (T + 1) * nx);  // second half: shift staging
-  ALLOC(o->d_us, 2 * B * T * nu);
-  ALLOC(o->d_x0, B * nx);
-  ALLOC(o->d_Kws, B * T * nu * nx);
-  ALLOC(o->d_kws, B * T * nu);
-  ALLOC(o->d_Kout, B * T * nu * nx);
-  ALLOC(o->d_dx, B * (T + 1) * nx);
-  ALLOC(o->d_du, B * T * nu);
-  ALLOC(o->d_w, B * T * nu);
-  ALLOC(o->d_nodestat, B * (T + 1) * 4);
-  ALLOC(o->d_qt, B * (T + 1) * (size_t)o->qt_size);
-  ALLOC(o->d_aux, B * (T + 1) * (size_t)o->aux_size);
-  ALLOC(o->d_ref, B * (T + 1) * (size_t)o->stride);
-  ALLOC(o->d_frames, B * (T + 1) * AGX_MAX_ROWS);
-  ALLOC(o->d_state, B);
-  ALLOC(o->d_ndone, 8);  // [0] finished instances, [1] instances whose ADMM loop has ended, [2] instances in the split line search
+  // every buffer the handle has from the start, zero-filled; the first allocation that fails ends the list
+  hipError_t bad = hipSuccess;
+  auto alloc = [&](auto **field, size_t count) { if (bad == hipSuccess) bad = o->own.device(field, count, true); };
+  alloc(&o->d_model, 1);
+  alloc(&o->d_ocp, o->cost_wide ? 2 : 1);  // wide cost sets: [1] the copy K1 reads
+  if (o->cost_wide) alloc(&o->d_cw, 1);
+  alloc(&o->d_dt, T);
+  alloc(&o->d_xs, 2 * B * (T + 1) * nx);  // second half: shift staging
+  alloc(&o->d_us, 2 * B * T * nu);
+  alloc(&o->d_x0, B * nx);
+  alloc(&o->d_Kws, B * T * nu * nx);
+  alloc(&o->d_kws, B * T * nu);
+  alloc(&o->d_Kout, B * T * nu * nx);
+  alloc(&o->d_dx, B * (T + 1) * nx);
+  alloc(&o->d_du, B * T * nu);
+  alloc(&o->d_w, B * T * nu);
+  alloc(&o->d_nodestat, B * (T + 1) * 4);
+  alloc(&o->d_qt, B * (T + 1) * (size_t)o->qt_size);
+  alloc(&o->d_aux, B * (T + 1) * (size_t)o->aux_size);
+  alloc(&o->d_ref, B * (T + 1) * (size_t)o->stride);
+  alloc(&o->d_frames, B * (T + 1) * AGX_MAX_ROWS);
+  alloc(&o->d_state, B);
+  alloc(&o->d_ndone, 8);  // [0] finished instances, [1] instances whose ADMM loop has ended, [2] instances in the split line search
   if (o->nv > 8) {
     for (int t = 0; t < o->T; ++t)
       if (o->dt[t] != o->dt[0]) o->shift_nodes.push_back(t);
-    if (!o->shift_nodes.empty()) {
-      ALLOC(o->d_shift_nodes, o->shift_nodes.size());
-      (void)hipMemcpy(o->d_shift_nodes, o->shift_nodes.data(), sizeof(int) * o->shift_nodes.size(), hipMemcpyHostToDevice);
-    }
+    if (!o->shift_nodes.empty()) alloc(&o->d_shift_nodes, o->shift_nodes.size());
   }
-  if (o->general) ALLOC(o->d_auxg, B * (T + 1) * (size_t)(3 * o->nv * 8));
+  if (o->general) alloc(&o->d_auxg, B * (T + 1) * (size_t)(3 * o->nv * 8));
   if (o->has_con) {
-    if (!o->d_qt2) ALLOC(o->d_qt2, B * (T + 1) * (size_t)o->qt_size);
+    alloc(&o->d_qt2, B * (T + 1) * (size_t)o->qt_size);
     const size_t cs = (size_t)o->con_cs;  // AGX_MAX_NC, wide sets: their own stride
-    ALLOC(o->d_cg, B * (T + 1) * cs);
-    if (o->con_wide) ALLOC(o->d_cjac, B * (T + 1) * (size_t)o->ho.cons[0].jstride * 8);  // distance gradients, d/dq only
-    else ALLOC(o->d_cjac, B * (T + 1) * AGX_MAX_DENSE * 32);  // 24 per row up to 7 joints (q | v | u, 8 each), 32 above (q only)
-    ALLOC(o->d_y, B * (T + 1) * cs);
-    ALLOC(o->d_z, B * (T + 1) * cs);
-    ALLOC(o->d_cx, B * (T + 1) * nx);
-    ALLOC(o->d_admmstat, B * (T + 1) * 4);
-    ALLOC(o->d_fac, B * T * 192);
-    ALLOC(o->d_segP, B * agx::kSeg * 256);
+    alloc(&o->d_cg, B * (T + 1) * cs);
+    if (o->con_wide) alloc(&o->d_cjac, B * (T + 1) * (size_t)o->ho.cons[0].jstride * 8);  // distance gradients, d/dq only
+    else alloc(&o->d_cjac, B * (T + 1) * AGX_MAX_DENSE * 32);  // 24 per row up to 7 joints (q | v | u, 8 each), 32 above (q only)
+    alloc(&o->d_y, B * (T + 1) * cs);
+    alloc(&o->d_z, B * (T + 1) * cs);
+    alloc(&o->d_cx, B * (T + 1) * nx);
+    alloc(&o->d_admmstat, B * (T + 1) * 4);
+    alloc(&o->d_fac, B * T * 192);
+    alloc(&o->d_segP, B * agx::kSeg * 256);
     if (const char *e = getenv("AGX_ADMM_SEGMENTS")) o->admm_segments = (e[0] != '0');
     if (const char *e = getenv("AGX_ADMM_PREFACTOR")) o->admm_prefactor = (e[0] != '0');
   }
-#undef ALLOC
-  // the polled hand-off needs FINE-GRAINED host memory (the stamp must not overtake the data it guards): ask for it
-  // explicitly; when the runtime cannot give it, fall back to stream-ordered copies + synchronize
-  if (hipHostMalloc((void **)&o->h_ndone, 16 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-    (void)hipGetLastError();
-    o->poll = false;
-    if (hipHostMalloc((void **)&o->h_ndone, 16 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { agx_ocp_destroy(o); return fail("hipHostMalloc failed"); }
-  }
+  if (bad != hipSuccess) return bail(std::string("agx_ocp_create: hipMalloc: ") + hipGetErrorString(bad));
+  o->d_ocp_k1 = o->d_ocp;
+  if (o->d_shift_nodes) (void)hipMemcpy(o->d_shift_nodes, o->shift_nodes.data(), sizeof(int) * o->shift_nodes.size(), hipMemcpyHostToDevice);
+  if (pinned_polled(o, &o->h_ndone, 16 * sizeof(unsigned long long))) return bail("hipHostMalloc failed");
   std::memset(o->h_ndone, 0xff, 16 * sizeof(unsigned long long));
   if (o->poll && hipHostGetDevicePointer((void **)&o->h_ndone_dev, o->h_ndone, 0) != hipSuccess) o->poll = false;
   if (const char *e = getenv("AGX_HOST_POLL")) o->poll = o->poll && (e[0] != '0');
   if (hipMemcpy(o->d_model, &o->hm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(o->d_ocp, &o->ho, sizeof(DevOcp), hipMemcpyHostToDevice) != hipSuccess ||
       (o->cost_wide && hipMemcpy(o->d_cw, &o->hw, sizeof(DevCostWide), hipMemcpyHostToDevice) != hipSuccess) ||
-      hipMemcpy(o->d_dt, o->dt.data(), sizeof(double) * T, hipMemcpyHostToDevice) != hipSuccess) {
-    agx_ocp_destroy(o);
-    return fail("agx_ocp_create: upload of the problem description failed");
-  }
+      hipMemcpy(o->d_dt, o->dt.data(), sizeof(double) * T, hipMemcpyHostToDevice) != hipSuccess)
+    return bail("agx_ocp_create: upload of the problem description failed");
   if (o->cost_wide) {
     DevOcp k1 = o->ho;
     k1.stride = std::max(1, std::max(o->hw.lay[0].prefix, o->hw.lay[1].prefix));
     o->d_ocp_k1 = o->d_ocp + 1;
-    if (hipMemcpy(o->d_ocp_k1, &k1, sizeof(DevOcp), hipMemcpyHostToDevice) != hipSuccess) { agx_ocp_destroy(o); return fail("agx_ocp_create: upload of the problem description failed"); }
+    if (hipMemcpy(o->d_ocp_k1, &k1, sizeof(DevOcp), hipMemcpyHostToDevice) != hipSuccess) return bail("agx_ocp_create: upload of the problem description failed");
   }
-  if (hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking) != hipSuccess) { agx_ocp_destroy(o); return fail("hipStreamCreate failed"); }
+  if (hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking) != hipSuccess) return bail("hipStreamCreate failed");
   o->own_stream = true;
-  (void)hipEventCreate(&o->ev0);
-  (void)hipEventCreate(&o->ev1);
-  (void)hipEventCreateWithFlags(&o->ev_done, hipEventDisableTiming);
-  o->rv.base = o->d_ref;
-  o->rv.bstride = (long long)(T + 1) * o->stride;
-  o->rv.tstride = o->stride;
-  o->rv.term_off = 0;
-  o->rv.frames = nullptr;
-  if (reset_state(o) || hipStreamSynchronize(o->stream) != hipSuccess) { agx_ocp_destroy(o); return fail("agx_ocp_create: state reset failed"); }
+  (void)o->own.event(&o->ev0);
+  (void)o->own.event(&o->ev1);
+  (void)o->own.event(&o->ev_done, hipEventDisableTiming);
+  rv_own_tile(o, nullptr);
+  if (reset_state(o) || hipStreamSynchronize(o->stream) != hipSuccess) return bail("agx_ocp_create: state reset failed");
   *out = o;
   return 0;
 }
@@ -1858,32 +1479,9 @@ void agx_ocp_destroy(agx_ocp *o) {
   if (!o) return;
   (void)hipSetDevice(o->device);
   if (o->stream) (void)hipStreamSynchronize(o->stream);
-  if (o->copy_stream) (void)hipStreamSynchronize(o->copy_stream);
-  void *ptrs[] = {o->d_mx2_elem, o->d_mx2_bnd, o->d_mx2_cl, o->d_ref_back, o->d_frames_back, o->d_snap, o->d_model, o->d_ocp, o->d_dt, o->d_xs, o->d_us, o->d_x0, o->d_tiles, o->d_Kws, o->d_kws, o->d_Kout, o->d_dx,
-                  o->d_du, o->d_ref, o->d_frames, o->d_state, o->d_ndone, o->d_scratch, o->d_traj, o->d_pts, o->d_sine, o->d_qt, o->d_aux, o->d_w, o->d_nodestat,
-                  o->d_qt2, o->d_cg, o->d_cjac, o->d_y, o->d_z, o->d_cx, o->d_admmstat, o->d_fac, o->d_hidx, o->d_auxg, o->d_shift_nodes, o->d_segP, o->d_Kws_lqr, o->d_kws_lqr, o->d_plant, o->d_minert, o->d_cw, o->d_obs,
-                  o->d_log, o->d_log_n, o->d_items};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  if (o->h_ndone) (void)hipHostFree(o->h_ndone);
-  if (o->ev0) (void)hipEventDestroy(o->ev0);
-  if (o->ev1) (void)hipEventDestroy(o->ev1);
-  if (o->ev_done) (void)hipEventDestroy(o->ev_done);
-  if (o->ev_refs) (void)hipEventDestroy(o->ev_refs);
-  if (o->ev_snap) (void)hipEventDestroy(o->ev_snap);
-  if (o->ev_dl) (void)hipEventDestroy(o->ev_dl);
-  for (int i = 0; i < 2; ++i) {
-    if (o->d_st_stage[i]) (void)hipFree(o->d_st_stage[i]);
-    if (o->st_host[i]) (void)hipHostFree(o->st_host[i]);
-    if (o->ev_st[i]) (void)hipEventDestroy(o->ev_st[i]);
-    for (hipEvent_t e : o->st_tev[i]) (void)hipEventDestroy(e);
-  }
-  if (o->ev_st_solver) (void)hipEventDestroy(o->ev_st_solver);
-  if (o->copy_stream) (void)hipStreamDestroy(o->copy_stream);
-  if (o->d_first && !o->poll) (void)hipFree(o->d_first);
-  if (o->h_first) (void)hipHostFree(o->h_first);
+  if (o->copy_stream) { (void)hipStreamSynchronize(o->copy_stream); (void)hipStreamDestroy(o->copy_stream); }
   if (o->own_stream && o->stream) (void)hipStreamDestroy(o->stream);
-  delete o;
+  delete o;  // (the owner frees what the handle still holds)
 }
 
 int agx_ocp_set_stream(agx_ocp *o, void *hip_stream) {
@@ -1962,11 +1560,7 @@ int agx_ocp_set_refs(agx_ocp *o, const double *ref_tile, const int32_t *frame_id
   HIPCHK(hipMemcpyAsync(o->d_ref, ref_tile, sizeof(double) * n * o->stride, hipMemcpyHostToDevice, o->stream));
   if (frame_ids) HIPCHK(hipMemcpyAsync(o->d_frames, frame_ids, sizeof(int) * n * AGX_MAX_ROWS, hipMemcpyHostToDevice, o->stream));
   HIPCHK(hipStreamSynchronize(o->stream));  // the caller may reuse its buffers
-  o->rv.base = o->d_ref;
-  o->rv.bstride = (long long)(o->T + 1) * o->stride;
-  o->rv.tstride = o->stride;
-  o->rv.term_off = 0;
-  o->rv.frames = frame_ids ? o->d_frames : nullptr;
+  rv_own_tile(o, frame_ids ? o->d_frames : nullptr);
   return 0;
 }
 
@@ -1986,20 +1580,15 @@ int agx_ocp_set_refs_device(agx_ocp *o, const double *d_ref_tile, const int32_t 
     HIPCHK(hipMemcpyAsync(o->d_ref, o->stage.data(), sizeof(double) * n * o->stride, hipMemcpyHostToDevice, o->stream));
     if (d_frame_ids) HIPCHK(hipMemcpyAsync(o->d_frames, d_frame_ids, sizeof(int) * n * AGX_MAX_ROWS, hipMemcpyDeviceToDevice, o->stream));
     HIPCHK(hipStreamSynchronize(o->stream));
-    o->rv.base = o->d_ref;
-    o->rv.frames = d_frame_ids ? o->d_frames : nullptr;
-  } else if (adopt) {
+    rv_own_tile(o, d_frame_ids ? o->d_frames : nullptr);
+  } else if (adopt) {  // the caller's memory, in the layout of the handle's own tile: the owner never sees it
+    rv_own_tile(o, d_frame_ids);
     o->rv.base = d_ref_tile;
-    o->rv.frames = d_frame_ids;
   } else {
     HIPCHK(hipMemcpyAsync(o->d_ref, d_ref_tile, sizeof(double) * n * o->stride, hipMemcpyDeviceToDevice, o->stream));
     if (d_frame_ids) HIPCHK(hipMemcpyAsync(o->d_frames, d_frame_ids, sizeof(int) * n * AGX_MAX_ROWS, hipMemcpyDeviceToDevice, o->stream));
-    o->rv.base = o->d_ref;
-    o->rv.frames = d_frame_ids ? o->d_frames : nullptr;
+    rv_own_tile(o, d_frame_ids ? o->d_frames : nullptr);
   }
-  o->rv.bstride = (long long)(o->T + 1) * o->stride;
-  o->rv.tstride = o->stride;
-  o->rv.term_off = 0;
   return 0;
 }
 
@@ -2020,8 +1609,8 @@ int agx_ocp_set_refs_async(agx_ocp *o, const double *ref_tile, const int32_t *fr
   if (carry_invalidate(o)) return -1;
   if (ensure_copy_stream(o)) return -1;
   const size_t n = (size_t)o->B * (o->T + 1);
-  if (!o->d_ref_back) HIPCHK(hipMalloc((void **)&o->d_ref_back, sizeof(double) * n * o->stride));
-  if (frame_ids && !o->d_frames_back) HIPCHK(hipMalloc((void **)&o->d_frames_back, sizeof(int) * n * AGX_MAX_ROWS));
+  if (!o->d_ref_back) HIPCHK(o->own.device(&o->d_ref_back, n * o->stride));
+  if (frame_ids && !o->d_frames_back) HIPCHK(o->own.device(&o->d_frames_back, n * AGX_MAX_ROWS));
   if (o->refs_pending) HIPCHK(hipEventSynchronize(o->ev_refs));  // a second upload before any solve: replaces the first
   // the back tile is free: the solve that read it has returned (solves are synchronous to the host)
   if (o->padded) {  // repacked through the handle's staging vector: the copy has to finish before this call returns
@@ -2062,7 +1651,7 @@ int agx_ocp_download_async(agx_ocp *o, double *xs, double *us, double *K) {
     return 0;
   }
   const size_t n_xs = B * (T + 1) * nx, n_us = B * T * nu, n_K = B * T * nu * nx;
-  if (!o->d_snap) HIPCHK(hipMalloc((void **)&o->d_snap, sizeof(double) * (n_xs + n_us + n_K)));
+  if (!o->d_snap) HIPCHK(o->own.device(&o->d_snap, n_xs + n_us + n_K));
   if (o->dl_pending) HIPCHK(hipEventSynchronize(o->ev_dl));  // the previous download still reads the snapshot
   // snapshot in the solver's stream (device to device, ~0.1 ms for 100 MB), then the copy engine drains it while the
   // solver goes on with the next step
@@ -2145,16 +1734,9 @@ int agx_ocp_first_packed(agx_ocp *o, const double **host, int *stride) {
   if (set_device(o)) return -1;
   const int FS = o->nu + o->nu * o->nx + o->nx + 8;
   if (!o->h_first) {
-    if (o->poll && hipHostMalloc((void **)&o->h_first, sizeof(double) * (size_t)o->B * FS, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-      (void)hipGetLastError();
-      o->poll = false;  // no fine-grained mapped memory: copy + synchronize from here on
-    }
-    if (!o->poll) HIPCHK(hipHostMalloc((void **)&o->h_first, sizeof(double) * (size_t)o->B * FS, hipHostMallocDefault));
-    if (o->poll) {
-      HIPCHK(hipHostGetDevicePointer((void **)&o->d_first, o->h_first, 0));  // the pack kernel writes host memory directly
-    } else {
-      HIPCHK(hipMalloc((void **)&o->d_first, sizeof(double) * (size_t)o->B * FS));
-    }
+    if (pinned_polled(o, &o->h_first, sizeof(double) * (size_t)o->B * FS)) return -1;
+    if (o->poll) HIPCHK(hipHostGetDevicePointer((void **)&o->d_first, o->h_first, 0));  // the pack kernel writes host memory directly: a view, not registered
+    else HIPCHK(o->own.device(&o->d_first, (size_t)o->B * FS));
     o->first_stride = FS;
   }
   const long long n = (long long)o->B * FS;
@@ -2418,14 +2000,12 @@ int agx_ocp_iter_log(agx_ocp *o, int capacity) {
   if (capacity < 0) return fail("agx_ocp_iter_log: negative capacity");
   if (set_device(o)) return -1;
   HIPCHK(hipStreamSynchronize(o->stream));  // (a queued log launch may still write the old arrays)
-  if (o->d_log) HIPCHK(hipFree(o->d_log));
-  if (o->d_log_n) HIPCHK(hipFree(o->d_log_n));
-  o->d_log = nullptr;
-  o->d_log_n = nullptr;
+  o->own.release(&o->d_log);
+  o->own.release(&o->d_log_n);
   o->log_cap = 0;
   if (capacity == 0) return 0;
-  HIPCHK(hipMalloc((void **)&o->d_log, sizeof(agx_iter_record) * (size_t)o->B * capacity));
-  HIPCHK(hipMalloc((void **)&o->d_log_n, sizeof(int) * (size_t)o->B));
+  HIPCHK(o->own.device(&o->d_log, (size_t)o->B * capacity));
+  HIPCHK(o->own.device(&o->d_log_n, (size_t)o->B));
   HIPCHK(hipMemsetAsync(o->d_log, 0, sizeof(agx_iter_record) * (size_t)o->B * capacity, o->stream));
   HIPCHK(hipMemsetAsync(o->d_log_n, 0, sizeof(int) * (size_t)o->B, o->stream));
   o->log_cap = capacity;
@@ -2451,10 +2031,8 @@ int agx_ocp_item_costs(agx_ocp *o, double *cost_r, double *Lx_r, double *Lu_r, d
   const int Rr = o->n_rows_all[0], Rt = o->n_rows_all[1], R = std::max(std::max(Rr, Rt), 1);
   const size_t units = (size_t)B * (T + 1) * R, total = units * (1 + NX + NU);
   if (sizeof(double) * total > o->items_bytes) {
-    if (o->d_items) { HIPCHK(hipStreamSynchronize(o->stream)); HIPCHK(hipFree(o->d_items)); }
-    o->d_items = nullptr;
-    o->items_bytes = 0;
-    HIPCHK(hipMalloc((void **)&o->d_items, sizeof(double) * total));
+    if (o->d_items) HIPCHK(hipStreamSynchronize(o->stream));  // (a queued launch may still write the old block)
+    HIPCHK(o->own.device(&o->d_items, total));
     o->items_bytes = sizeof(double) * total;
   }
   double *d_cost = o->d_items, *d_Lx = d_cost + units, *d_Lu = d_Lx + units * NX;
@@ -2651,376 +2229,6 @@ int agx_ocp_profile(agx_ocp *o, int enable, double *ms_sum, long long *count) {
   return 0;
 }
 
-// Wide cost sets: k_sine_fill has written the rows of the prefix; the pair rows of every sample get [row.weight (or the scheduled
-// item weight gw_item [B][n_points], device) | 1].
-static int traj_fill_pairs(agx_ocp *o, const double *d_gw_item) {
-  if (!o->cost_wide) return 0;
-  const long long units = (long long)o->B * o->n_points;
-  HIPCHK((hipError_t)agx_cost_pairs_fill_launch((void *)o->stream, o->d_cw, d_gw_item, o->d_traj, units, o->stride));
-  return 0;
-}
-
-// The resident generators track ONE end-effector frame: frame-based cost rows look at it on every node
-// (what the host path does per node with `obj.id = ...`, ocp_croco_generic.py:208).
-static int traj_frames(agx_ocp *o, int frame) {
-  std::vector<int> fr((size_t)o->B * (o->T + 1) * AGX_MAX_ROWS, -1);
-  for (int b = 0; b < o->B; ++b)
-    for (int t = 0; t <= o->T; ++t) {
-      const DevRows &rows = o->ho.rows[t == o->T ? 1 : 0];
-      for (int r = 0; r < rows.n; ++r)
-        if (rows.kind[r] == AGX_RES_FRAME_PLACEMENT || rows.kind[r] == AGX_RES_FRAME_TRANSLATION || rows.kind[r] == AGX_RES_FRAME_ROTATION)
-          fr[((size_t)b * (o->T + 1) + t) * AGX_MAX_ROWS + r] = frame;
-    }
-  HIPCHK(hipMemcpyAsync(o->d_frames, fr.data(), sizeof(int) * fr.size(), hipMemcpyHostToDevice, o->stream));
-  HIPCHK(hipStreamSynchronize(o->stream));
-  o->frames_set = true;
-  o->frames_uniform = true;
-  return 0;
-}
-
-int agx_traj_sine_create(agx_ocp *o, int n_points, double dt, const double *q0, const double *amp, const double *pulsation,
-                         const double *scale_duration, const double *t0, const double *w_q, const double *w_qdot,
-                         const double *w_effort, const double *w_pose, int frame) {
-  if (!o || !q0 || !amp || !pulsation || !scale_duration || !t0 || !w_q || !w_qdot || !w_effort || !w_pose)
-    return fail("agx_traj_sine_create: null argument");
-  if (n_points < o->T + 1) return fail("agx_traj_sine_create: need at least T+1 samples");
-  if (frame < 0 || frame >= o->hm.nframes) return fail("agx_traj_sine_create: frame id out of range");
-  if (set_device(o)) return -1;
-  if (carry_invalidate(o)) return -1;
-  if (stream_end(o)) return -1;
-  const size_t B = o->B, nv = o->nv;
-  if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
-  if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
-  if (o->d_sine) { (void)hipFree(o->d_sine); o->d_sine = nullptr; }
-  HIPCHK(hipMalloc((void **)&o->d_traj, sizeof(double) * B * n_points * 2 * o->stride));
-  HIPCHK(hipMalloc((void **)&o->d_pts, sizeof(double) * B * n_points * (4 * nv + 12)));
-  HIPCHK(hipMalloc((void **)&o->d_sine, sizeof(double) * (4 * B * nv + B)));
-  double *d = o->d_sine;
-  // pad joints: amplitude 0 (they stay at rest), scale duration 1 (it divides)
-  if (up(o, d, q0, B, 1) || up(o, d + B * nv, amp, B, 1) || up(o, d + 2 * B * nv, pulsation, B, 1) || up(o, d + 3 * B * nv, scale_duration, B, 1, 1.0)) return -1;
-  HIPCHK(hipMemcpyAsync(d + 4 * B * nv, t0, sizeof(double) * B, hipMemcpyHostToDevice, o->stream));
-  agx::SineParams sp;
-  std::memset(&sp, 0, sizeof(sp));
-  sp.q0 = d; sp.amp = d + B * nv; sp.puls = d + 2 * B * nv; sp.scale = d + 3 * B * nv; sp.t0 = d + 4 * B * nv;
-  for (size_t i = 0; i < nv; ++i) {  // pad joints: weight 1 on an identically zero residual
-    const bool real = i < (size_t)o->nvu;
-    sp.w_q[i] = real ? w_q[i] : 1.0; sp.w_qdot[i] = real ? w_qdot[i] : 1.0; sp.w_effort[i] = real ? w_effort[i] : 1.0;
-  }
-  for (int i = 0; i < 6; ++i) sp.w_pose[i] = w_pose[i];
-  sp.dt = dt; sp.n_points = n_points; sp.frame = frame;
-  o->n_points = n_points;
-  int rc = dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
-    constexpr int NV = decltype(NVc)::value;
-    constexpr bool CH = decltype(CHc)::value;
-    const long long units = (long long)B * n_points;
-    hipLaunchKernelGGL((agx::k_sine_fill<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, sp, o->d_traj, o->d_pts);
-    HIPCHK(hipGetLastError());
-    return 0;
-  });
-  if (rc) return rc;
-  if (traj_fill_pairs(o, sp.gw_item)) return -1;
-  HIPCHK(hipStreamSynchronize(o->stream));
-  if (traj_frames(o, frame)) return -1;
-  return agx_traj_set_window(o, 0);
-}
-
-// The caller-fed resident trajectory behind agx_traj_generic_create / agx_traj_generic_create_weighted (`fn`: the entry point, for
-// the messages).  pose / gw_pose / gw_item: optional per-sample arrays [B][n_points][12] / [6] / [1] (host); w_pose: the constant
-// pose weights used without gw_pose.
-static int traj_generic_build(agx_ocp *o, const char *fn, int n_points, const double *q, const double *dq, const double *ddq,
-                              const double *w_q, const double *w_qdot, const double *w_effort, const double *w_pose, int frame,
-                              const double *pose, const double *gw_pose, const double *gw_item) {
-  const std::string name(fn);
-  if (n_points < o->T + 1) return fail(name + ": trajectory shorter than the horizon");
-  if (frame < 0 || frame >= o->hm.nframes) return fail(name + ": frame id out of range");
-  if (set_device(o)) return -1;
-  if (carry_invalidate(o)) return -1;
-  if (stream_end(o)) return -1;
-  const size_t B = o->B, nv = o->nv, np = B * (size_t)n_points, n = np * nv;
-  if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
-  if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
-  if (o->d_sine) { (void)hipFree(o->d_sine); o->d_sine = nullptr; }
-  HIPCHK(hipMalloc((void **)&o->d_traj, sizeof(double) * B * n_points * 2 * o->stride));
-  HIPCHK(hipMalloc((void **)&o->d_pts, sizeof(double) * B * n_points * (4 * nv + 12)));
-  // q | dq | ddq samples, then the optional per-sample poses, pose weights and collision item weights
-  HIPCHK(hipMalloc((void **)&o->d_sine, sizeof(double) * (3 * n + (pose ? 12 * np : 0) + (gw_pose ? 6 * np : 0) + (gw_item ? np : 0))));
-  double *d = o->d_sine;
-  if (up(o, d, q, np, 1) || up(o, d + n, dq, np, 1) || up(o, d + 2 * n, ddq, np, 1)) return -1;
-  agx::SineParams sp;
-  std::memset(&sp, 0, sizeof(sp));
-  sp.gq = d; sp.gdq = d + n; sp.gddq = d + 2 * n;
-  double *extra = d + 3 * n;
-  if (pose) {
-    HIPCHK(hipMemcpyAsync(extra, pose, sizeof(double) * 12 * np, hipMemcpyHostToDevice, o->stream));
-    sp.gpose = extra; extra += 12 * np;
-  }
-  if (gw_pose) {
-    HIPCHK(hipMemcpyAsync(extra, gw_pose, sizeof(double) * 6 * np, hipMemcpyHostToDevice, o->stream));
-    sp.gw_pose = extra; extra += 6 * np;
-  }
-  if (gw_item) {
-    HIPCHK(hipMemcpyAsync(extra, gw_item, sizeof(double) * np, hipMemcpyHostToDevice, o->stream));
-    sp.gw_item = extra;
-  }
-  for (size_t i = 0; i < nv; ++i) {  // pad joints: weight 1 on an identically zero residual
-    const bool real = i < (size_t)o->nvu;
-    sp.w_q[i] = real ? w_q[i] : 1.0; sp.w_qdot[i] = real ? w_qdot[i] : 1.0; sp.w_effort[i] = real ? w_effort[i] : 1.0;
-  }
-  if (w_pose)
-    for (int i = 0; i < 6; ++i) sp.w_pose[i] = w_pose[i];
-  sp.dt = 0.0; sp.n_points = n_points; sp.frame = frame;
-  o->n_points = n_points;
-  int rc = dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
-    constexpr int NV = decltype(NVc)::value;
-    constexpr bool CH = decltype(CHc)::value;
-    const long long units = (long long)B * n_points;
-    hipLaunchKernelGGL((agx::k_sine_fill<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, sp, o->d_traj, o->d_pts);
-    HIPCHK(hipGetLastError());
-    return 0;
-  });
-  if (rc) return rc;
-  if (traj_fill_pairs(o, sp.gw_item)) return -1;
-  HIPCHK(hipStreamSynchronize(o->stream));
-  if (traj_frames(o, frame)) return -1;
-  return agx_traj_set_window(o, 0);
-}
-
-int agx_traj_generic_create(agx_ocp *o, int n_points, const double *q, const double *dq, const double *ddq, const double *w_q,
-                            const double *w_qdot, const double *w_effort, const double *w_pose, int frame) {
-  if (!o || !q || !dq || !ddq || !w_q || !w_qdot || !w_effort || !w_pose) return fail("agx_traj_generic_create: null argument");
-  return traj_generic_build(o, "agx_traj_generic_create", n_points, q, dq, ddq, w_q, w_qdot, w_effort, w_pose, frame, nullptr, nullptr, nullptr);
-}
-
-int agx_traj_generic_create_weighted(agx_ocp *o, int n_points, const double *q, const double *dq, const double *ddq, const double *w_q,
-                                     const double *w_qdot, const double *w_effort, int frame, const double *pose, const double *w_pose,
-                                     const double *w_collision) {
-  if (!o || !q || !dq || !ddq || !w_q || !w_qdot || !w_effort || !w_pose) return fail("agx_traj_generic_create_weighted: null argument");
-  return traj_generic_build(o, "agx_traj_generic_create_weighted", n_points, q, dq, ddq, w_q, w_qdot, w_effort, nullptr, frame, pose, w_pose,
-                            w_collision);
-}
-
-// The Cartesian sine generators: `period` null = agx_traj_cartesian_sine_create, set = the weight-increasing variant (`fn`: the entry
-// point, for the messages).
-static int traj_cartesian_build(agx_ocp *o, const char *fn, int n_points, double dt, const double *q0, const double *amp, const double *pulsation,
-                                double scale_duration, double precision, int it_max, const double *w_q, const double *w_qdot,
-                                const double *w_effort, const double *w_pose, int frame, const double *period, double max_weight, double rate) {
-  const std::string name(fn);
-  if (n_points < o->T + 1) return fail(name + ": trajectory shorter than the horizon");
-  if (frame < 0 || frame >= o->hm.nframes) return fail(name + ": frame id out of range");
-  if (!(scale_duration > 0.0) || !(precision > 0.0) || it_max < 1) return fail(name + ": scale_duration, precision, it_max must be positive");
-  if (o->nv > 7) return fail(name + ": nv <= 7");
-  if (period) {
-    for (size_t i = 0; i < (size_t)o->B * 3; ++i)
-      if (!(period[i] > 0.0) || !std::isfinite(period[i])) return fail(name + ": periods must be positive");
-    if (!std::isfinite(max_weight) || !std::isfinite(rate)) return fail(name + ": max_weight and rate must be finite");
-  }
-  if (set_device(o)) return -1;
-  if (carry_invalidate(o)) return -1;
-  if (stream_end(o)) return -1;
-  const size_t B = o->B, nv = o->nv, n = B * (size_t)n_points * nv;
-  if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
-  if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
-  if (o->d_sine) { (void)hipFree(o->d_sine); o->d_sine = nullptr; }
-  HIPCHK(hipMalloc((void **)&o->d_traj, sizeof(double) * B * n_points * 2 * o->stride));
-  HIPCHK(hipMalloc((void **)&o->d_pts, sizeof(double) * B * n_points * (4 * nv + 12)));
-  // q | dq | ddq samples, then the per-instance parameters q0 | amp | pulsation | period, the poses, the scheduled pose weights
-  // (weight-increasing variant) and the failure flags
-  const size_t npar = B * (nv + 9), npose = B * (size_t)n_points * 12, nw = period ? B * (size_t)n_points * 6 : 0;
-  o->n_points = 0;  // until the trajectory is complete: a failed build leaves nothing a later window / MPC step could consume
-  HIPCHK(hipMalloc((void **)&o->d_sine, sizeof(double) * (3 * n + npar + npose + nw) + sizeof(int) * B));
-  double *d = o->d_sine, *dpar = d + 3 * n, *dpose = dpar + npar, *dw = dpose + npose;
-  int *dfail = reinterpret_cast<int *>(dw + nw);
-  HIPCHK(hipMemsetAsync(d + 2 * n, 0, sizeof(double) * n, o->stream));  // ddq = 0
-  if (up(o, dpar, q0, B, 1)) return -1;
-  HIPCHK(hipMemcpyAsync(dpar + B * nv, amp, sizeof(double) * B * 3, hipMemcpyHostToDevice, o->stream));
-  HIPCHK(hipMemcpyAsync(dpar + B * nv + B * 3, pulsation, sizeof(double) * B * 3, hipMemcpyHostToDevice, o->stream));
-  if (period) HIPCHK(hipMemcpyAsync(dpar + B * nv + B * 6, period, sizeof(double) * B * 3, hipMemcpyHostToDevice, o->stream));
-  agx::CartSineParams cp;
-  std::memset(&cp, 0, sizeof(cp));
-  cp.q0 = dpar; cp.amp = dpar + B * nv; cp.puls = dpar + B * nv + B * 3;
-  cp.dt = dt; cp.scale = scale_duration; cp.precision = precision;
-  cp.n_points = n_points; cp.frame = frame; cp.it_max = it_max;
-  cp.q = d; cp.dq = d + n; cp.pose = dpose; cp.fail = dfail;
-  if (period) {
-    cp.period = dpar + B * nv + B * 6; cp.max_weight = max_weight; cp.rate = rate; cp.wpose = dw;
-    for (int i = 0; i < 3; ++i) cp.w_rot[i] = w_pose[3 + i];
-  }
-  agx::SineParams sp;
-  std::memset(&sp, 0, sizeof(sp));
-  sp.gq = d; sp.gdq = d + n; sp.gddq = d + 2 * n;
-  for (size_t i = 0; i < nv; ++i) {  // pad joints: weight 1 on an identically zero residual
-    const bool real = i < (size_t)o->nvu;
-    sp.w_q[i] = real ? w_q[i] : 1.0; sp.w_qdot[i] = real ? w_qdot[i] : 1.0; sp.w_effort[i] = real ? w_effort[i] : 1.0;
-  }
-  for (int i = 0; i < 6; ++i) sp.w_pose[i] = w_pose[i];
-  sp.dt = 0.0; sp.n_points = n_points; sp.frame = frame;
-  sp.gpose = dpose;
-  if (period) sp.gw_pose = dw;
-  int rc = dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
-    constexpr int NV = decltype(NVc)::value;
-    constexpr bool CH = decltype(CHc)::value;
-    if constexpr (NV <= 7) {
-      if (period) hipLaunchKernelGGL((agx::k_cartesian_sine_ik<NV, CH, true>), dim3((int)((B + 63) / 64)), dim3(64), 0, o->stream, o->d_model, (int)B, cp);
-      else hipLaunchKernelGGL((agx::k_cartesian_sine_ik<NV, CH>), dim3((int)((B + 63) / 64)), dim3(64), 0, o->stream, o->d_model, (int)B, cp);
-      const long long units = (long long)B * n_points;
-      hipLaunchKernelGGL((agx::k_sine_fill<NV, CH>), dim3((int)((units + 63) / 64)), dim3(64), 0, o->stream, o->d_model, o->d_ocp, sp, o->d_traj, o->d_pts);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-  });
-  if (rc) return rc;
-  if (traj_fill_pairs(o, sp.gw_item)) return -1;
-  std::vector<int> failed(B);
-  HIPCHK(hipMemcpyAsync(failed.data(), dfail, sizeof(int) * B, hipMemcpyDeviceToHost, o->stream));
-  HIPCHK(hipStreamSynchronize(o->stream));
-  for (size_t b = 0; b < B; ++b)
-    if (failed[b]) {
-      char msg[160];
-      std::snprintf(msg, sizeof(msg), "inverse kinematics failed to converge: instance %zu at point %d (it_max %d)", b, failed[b] - 1, it_max);
-      // nothing half-built stays behind: set_window / mpc_step refuse a handle without a trajectory
-      (void)hipFree(o->d_traj); o->d_traj = nullptr;
-      (void)hipFree(o->d_pts); o->d_pts = nullptr;
-      (void)hipFree(o->d_sine); o->d_sine = nullptr;
-      return fail(msg);
-    }
-  o->n_points = n_points;
-  if (traj_frames(o, frame)) return -1;
-  return agx_traj_set_window(o, 0);
-}
-
-int agx_traj_cartesian_sine_create(agx_ocp *o, int n_points, double dt, const double *q0, const double *amp, const double *pulsation,
-                                   double scale_duration, double precision, int it_max, const double *w_q, const double *w_qdot,
-                                   const double *w_effort, const double *w_pose, int frame) {
-  if (!o || !q0 || !amp || !pulsation || !w_q || !w_qdot || !w_effort || !w_pose) return fail("agx_traj_cartesian_sine_create: null argument");
-  return traj_cartesian_build(o, "agx_traj_cartesian_sine_create", n_points, dt, q0, amp, pulsation, scale_duration, precision, it_max, w_q, w_qdot,
-                              w_effort, w_pose, frame, nullptr, 0.0, 0.0);
-}
-
-int agx_traj_cartesian_sine_wi_create(agx_ocp *o, int n_points, double dt, const double *q0, const double *amp, const double *pulsation,
-                                      double scale_duration, double precision, int it_max, const double *w_q, const double *w_qdot,
-                                      const double *w_effort, const double *w_pose, int frame, const double *period, double max_weight,
-                                      double rate) {
-  if (!o || !q0 || !amp || !pulsation || !w_q || !w_qdot || !w_effort || !w_pose || !period)
-    return fail("agx_traj_cartesian_sine_wi_create: null argument");
-  return traj_cartesian_build(o, "agx_traj_cartesian_sine_wi_create", n_points, dt, q0, amp, pulsation, scale_duration, precision, it_max, w_q,
-                              w_qdot, w_effort, w_pose, frame, period, max_weight, rate);
-}
-
-int agx_traj_set_horizon_indexes(agx_ocp *o, const int32_t *idx) {
-  if (!o) return fail("null handle");
-  if (set_device(o)) return -1;
-  if (o->streamed && idx && idx[o->T] >= 0 && idx[o->T] + 1 > o->st_span)
-    return fail("agx_traj_set_horizon_indexes: the window covers idx[T] + 1 = " + std::to_string(idx[o->T] + 1) + " samples, the streamed trajectory was created with max_span " +
-                std::to_string(o->st_span));
-  if (carry_invalidate(o)) return -1;
-  o->hidx.clear();
-  if (!idx) return 0;  // back to uniform
-  bool uniform = true;
-  for (int t = 0; t <= o->T; ++t) {
-    if (idx[t] < 0 || (t > 0 && idx[t] <= idx[t - 1])) return fail("agx_traj_set_horizon_indexes: indexes must be non-negative and increasing");
-    uniform = uniform && idx[t] == t;
-  }
-  if (uniform) return 0;
-  o->hidx.assign(idx, idx + o->T + 1);
-  if (!o->d_hidx) HIPCHK(hipMalloc((void **)&o->d_hidx, sizeof(int) * (o->T + 1)));
-  HIPCHK(hipMemcpyAsync(o->d_hidx, o->hidx.data(), sizeof(int) * (o->T + 1), hipMemcpyHostToDevice, o->stream));
-  HIPCHK(hipStreamSynchronize(o->stream));
-  return 0;
-}
-
-int agx_traj_set_window(agx_ocp *o, int k0) {
-  if (!o) return fail("null handle");
-  if (!o->d_traj) return fail("agx_traj_set_window: no resident trajectory");
-  const int last = o->hidx.empty() ? o->T : o->hidx[o->T];
-  if (o->streamed && set_device(o)) return -1;
-  const int k0_logical = k0;
-  if (traj_locate(o, "agx_traj_set_window", "window leaves the trajectory", k0_logical, last + 1, &k0)) return -1;
-  o->win_logical = k0_logical;
-  o->win_k0 = k0;
-  o->rv.frames = o->d_frames;
-  if (o->hidx.empty()) {
-    o->rv.base = o->d_traj + (long long)k0 * 2 * o->stride;
-    o->rv.bstride = (long long)o->n_points * 2 * o->stride;
-    o->rv.tstride = 2 * o->stride;
-    o->rv.term_off = o->stride;
-    return 0;
-  }
-  if (set_device(o)) return -1;
-  const long long n = (long long)o->B * (o->T + 1) * o->stride;
-  hipLaunchKernelGGL(agx::k_gather_window, dim3((int)((n + 255) / 256)), dim3(256), 0, o->stream, o->d_traj, o->d_ref, o->d_hidx, o->B, o->T,
-                     o->stride, o->n_points, k0);
-  HIPCHK(hipGetLastError());
-  o->rv.base = o->d_ref;
-  o->rv.bstride = (long long)(o->T + 1) * o->stride;
-  o->rv.tstride = o->stride;
-  o->rv.term_off = 0;
-  return 0;
-}
-
-int agx_traj_get_point(agx_ocp *o, int k, double *q, double *v, double *a, double *u, double *pose) {
-  if (!o || !o->d_pts) return fail("agx_traj_get_point: no resident trajectory");
-  if (set_device(o)) return -1;
-  if (traj_locate(o, "agx_traj_get_point", "sample out of range", k, 1, &k)) return -1;
-  const size_t B = o->B, nv = o->nv, w = 4 * nv + 12;
-  std::vector<double> h(B * w);
-  HIPCHK(hipMemcpy2DAsync(h.data(), sizeof(double) * w, o->d_pts + (size_t)k * w, sizeof(double) * o->n_points * w, sizeof(double) * w, B, hipMemcpyDeviceToHost, o->stream));
-  HIPCHK(hipStreamSynchronize(o->stream));
-  for (size_t b = 0; b < B; ++b) {
-    const double *p = &h[b * w];
-    const size_t nvu = o->nvu;  // the sample's joint blocks hold nv (capacity) entries, the caller's nvu
-    if (q) std::memcpy(q + b * nvu, p, sizeof(double) * nvu);
-    if (v) std::memcpy(v + b * nvu, p + nv, sizeof(double) * nvu);
-    if (a) std::memcpy(a + b * nvu, p + 2 * nv, sizeof(double) * nvu);
-    if (u) std::memcpy(u + b * nvu, p + 3 * nv, sizeof(double) * nvu);
-    if (pose) std::memcpy(pose + b * 12, p + 4 * nv, sizeof(double) * 12);
-  }
-  return 0;
-}
-
-int agx_traj_get_tile(agx_ocp *o, int k, int terminal, double *out) {
-  if (!o || !out) return fail("agx_traj_get_tile: null argument");
-  if (!o->d_traj) return fail("agx_traj_get_tile: no resident trajectory");
-  if (set_device(o)) return -1;
-  if (traj_locate(o, "agx_traj_get_tile", "sample out of range", k, 1, &k)) return -1;
-  if (carry_invalidate(o)) return -1;
-  const size_t B = o->B, st = o->stride, su = o->stride_u;
-  const int lay = terminal ? 1 : 0;
-  std::vector<double> h(B * st);
-  HIPCHK(hipMemcpy2DAsync(h.data(), sizeof(double) * st, o->d_traj + ((size_t)k * 2 + lay) * st, sizeof(double) * o->n_points * 2 * st,
-                          sizeof(double) * st, B, hipMemcpyDeviceToHost, o->stream));
-  HIPCHK(hipStreamSynchronize(o->stream));
-  // the generators write the rows of the layout; what lies behind them in a slot of `stride` doubles is returned as zeros
-  const DevRows &R = o->ho.rows[lay];
-  const size_t used = (R.n ? (size_t)R.off[R.n - 1] + 1 + R.nref[R.n - 1] + R.nr[R.n - 1] : 0) + 2 * (size_t)o->hw.lay[lay].n;  // + the pair rows of a wide cost set
-  std::memset(out, 0, sizeof(double) * B * su);
-  for (size_t b = 0; b < B; ++b)
-    for (size_t e = 0; e < used; ++e) {
-      const int eu = o->padded ? o->refmap[lay][e] : (int)e;  // pad joints have no place in the caller's tile
-      if (eu >= 0) out[b * su + eu] = h[b * st + e];
-    }
-  return 0;
-}
-
-static int ws_from_ref(agx_ocp *o, int k0, int set_x0) {
-  const long long units = (long long)o->B * (o->T + 1);
-  hipLaunchKernelGGL(agx::k_ws_from_ref, dim3((int)((units + 255) / 256)), dim3(256), 0, o->stream, o->d_xs, o->d_us, o->d_x0, o->d_pts,
-                     o->B, o->T, o->nv, o->n_points, k0, set_x0, o->hidx.empty() ? nullptr : o->d_hidx);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int agx_traj_warmstart_from_reference(agx_ocp *o) {
-  if (!o || !o->d_pts) return fail("agx_traj_warmstart_from_reference: no resident trajectory");
-  if (set_device(o)) return -1;
-  if (o->streamed) {  // the window may have been released, or never set
-    int phys = 0;
-    if (o->win_logical < 0) return fail("agx_traj_warmstart_from_reference: no window set on the streamed trajectory");
-    if (traj_locate(o, "agx_traj_warmstart_from_reference", "", o->win_logical, (o->hidx.empty() ? o->T : o->hidx[o->T]) + 1, &phys)) return -1;
-  }
-  if (carry_invalidate(o)) return -1;
-  return ws_from_ref(o, o->win_k0, 1);
-}
-
 int agx_ocp_download_x0(agx_ocp *o, double *x0) {
   if (!o || !x0) return fail("agx_ocp_download_x0: null argument");
   if (set_device(o)) return -1;
@@ -3062,7 +2270,7 @@ static int upload_inertials(agx_ocp *o, const std::string &fn, const double *mas
   for (size_t k = 0; k < B * nvu * 9; ++k)
     if (!std::isfinite(inertia[k])) return fail(fn + ": non-finite inertia (instance " + std::to_string(k / (9 * nvu)) + ")");
   if (set_device(o)) return -1;
-  if (!*d_buf) HIPCHK(hipMalloc((void **)d_buf, sizeof(double) * B * w));
+  if (!*d_buf) HIPCHK(o->own.device(d_buf, B * w));
   // a kernel queued earlier may still read the buffer, and the copy below reads the image: both are the handle's own, so the
   // host waits for the stream before it rewrites the image, then uploads IN the solver's stream, behind everything queued
   HIPCHK(hipStreamSynchronize(o->stream));
@@ -3166,10 +2374,7 @@ int agx_ocp_set_obstacle_placements(agx_ocp *o, int n_frames, const int32_t *fra
   // stream before it touches either, then uploads IN that stream (as upload_inertials)
   HIPCHK(hipStreamSynchronize(o->stream));
   if (bytes > o->obs_bytes) {
-    void *p = nullptr;
-    HIPCHK(hipMalloc(&p, bytes));
-    if (o->d_obs) (void)hipFree(o->d_obs);
-    o->d_obs = p;
+    HIPCHK(o->own.device_bytes(&o->d_obs, bytes));
     o->obs_bytes = bytes;
   }
   o->obs_stage.assign(hd + B * n * 12, 0.0);
@@ -3257,207 +2462,6 @@ int agx_ocp_mpc_step(agx_ocp *o, int k0, int max_iter, int first) {
   (carry_mode != 0 ? o->steps_carried : o->steps_full) += 1;
   o->carry_armed = o->carry_static;
   o->carry_k0 = k0;
-  return 0;
-}
-
-// ---- streamed resident trajectory ---------------------------------------------------------------------------------------------
-// doubles one (instance, sample) of a staged chunk takes: q | dq | ddq at the capacity nv, pose 12, pose weights 6, collision weight 1
-static size_t stream_sample_doubles(const agx_ocp *o) { return 3 * (size_t)o->nv + 19; }
-
-int agx_traj_stream_create(agx_ocp *o, int capacity, int max_span, const double *w_q, const double *w_qdot, const double *w_effort,
-                           const double *w_pose, int frame) {
-  if (!o || !w_q || !w_qdot || !w_effort || !w_pose) return fail("agx_traj_stream_create: null argument");
-  if (max_span < o->T + 1) return fail("agx_traj_stream_create: max_span " + std::to_string(max_span) + " is below the T + 1 = " + std::to_string(o->T + 1) + " samples of a window");
-  if (capacity < max_span) return fail("agx_traj_stream_create: capacity " + std::to_string(capacity) + " is below max_span " + std::to_string(max_span));
-  if (frame < 0 || frame >= o->hm.nframes) return fail("agx_traj_stream_create: frame id out of range");
-  if ((long long)capacity + max_span - 1 > INT_MAX) return fail("agx_traj_stream_create: capacity + max_span - 1 does not fit an int");
-  // horizon indexes set earlier stay with the handle: their window must fit the mirror too (agx_traj_set_horizon_indexes checks later ones)
-  if (!o->hidx.empty() && o->hidx[o->T] + 1 > max_span)
-    return fail("agx_traj_stream_create: the horizon indexes of the handle cover idx[T] + 1 = " + std::to_string(o->hidx[o->T] + 1) +
-                " samples, max_span is " + std::to_string(max_span));
-  if (set_device(o)) return -1;
-  if (carry_invalidate(o)) return -1;
-  if (stream_end(o)) return -1;
-  if (ensure_copy_stream(o)) return -1;
-  const size_t B = o->B, nv = o->nv;
-  if (o->d_traj) { (void)hipFree(o->d_traj); o->d_traj = nullptr; }
-  if (o->d_pts) { (void)hipFree(o->d_pts); o->d_pts = nullptr; }
-  if (o->d_sine) { (void)hipFree(o->d_sine); o->d_sine = nullptr; }
-  o->n_points = 0;
-  // no window yet: the solver looks at the handle's own tile until agx_traj_set_window / agx_ocp_mpc_step finds one in the ring
-  o->rv.base = o->d_ref;
-  o->rv.bstride = (long long)(o->T + 1) * o->stride;
-  o->rv.tstride = o->stride;
-  o->rv.term_off = 0;
-  o->rv.frames = nullptr;
-  const size_t n_slots = (size_t)capacity + max_span - 1;
-  HIPCHK(hipMalloc((void **)&o->d_traj, sizeof(double) * B * n_slots * 2 * o->stride));
-  HIPCHK(hipMalloc((void **)&o->d_pts, sizeof(double) * B * n_slots * (4 * nv + 12)));
-  HIPCHK(hipMemsetAsync(o->d_traj, 0, sizeof(double) * B * n_slots * 2 * o->stride, o->stream));
-  HIPCHK(hipMemsetAsync(o->d_pts, 0, sizeof(double) * B * n_slots * (4 * nv + 12), o->stream));
-  o->st_chunk = max_span;
-  const size_t stage = sizeof(double) * B * (size_t)o->st_chunk * stream_sample_doubles(o);
-  for (int i = 0; i < 2; ++i) {
-    HIPCHK(hipHostMalloc((void **)&o->st_host[i], stage, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void **)&o->d_st_stage[i], stage));
-    if (!o->ev_st[i]) HIPCHK(hipEventCreateWithFlags(&o->ev_st[i], hipEventDisableTiming));
-  }
-  if (!o->ev_st_solver) HIPCHK(hipEventCreateWithFlags(&o->ev_st_solver, hipEventDisableTiming));
-  agx::SineParams &sp = o->st_sp;
-  std::memset(&sp, 0, sizeof(sp));
-  for (size_t i = 0; i < nv; ++i) {  // pad joints: weight 1 on an identically zero residual
-    const bool real = i < (size_t)o->nvu;
-    sp.w_q[i] = real ? w_q[i] : 1.0; sp.w_qdot[i] = real ? w_qdot[i] : 1.0; sp.w_effort[i] = real ? w_effort[i] : 1.0;
-  }
-  for (int i = 0; i < 6; ++i) sp.w_pose[i] = w_pose[i];
-  sp.dt = 0.0; sp.n_points = (int)n_slots; sp.frame = frame;
-  o->n_points = (int)n_slots;
-  o->st_cap = capacity; o->st_span = max_span; o->st_first = o->st_end = 0; o->st_next = 0;
-  o->win_logical = -1;
-  o->streamed = true;
-  return traj_frames(o, frame);  // (waits for the solver stream: the ring is zeroed when this returns)
-}
-
-}  // extern "C"
-namespace {
-// Transfer of the staged piece o->st_last and fill of its slots, on the copy stream.  behind_solver: the fill waits for what the
-// solver stream holds at this moment, which may still read the slots released since (the transfer need not wait: the device
-// half of a staging buffer is read by fills of the copy stream only).
-int stream_enqueue_last(agx_ocp *o, bool behind_solver) {
-  const auto &L = o->st_last;
-  if (behind_solver && stream_time_mark(o, 1, o->copy_stream)) return -1;
-  HIPCHK(hipMemcpyAsync(o->d_st_stage[L.buf], o->st_host[L.buf], sizeof(double) * L.used, hipMemcpyHostToDevice, o->copy_stream));
-  if (behind_solver) {
-    HIPCHK(hipEventRecord(o->ev_st_solver, o->stream));
-    HIPCHK(hipStreamWaitEvent(o->copy_stream, o->ev_st_solver, 0));
-  }
-  const long long units = (long long)o->B * L.m;
-  int rc = dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
-    constexpr int NV = decltype(NVc)::value;
-    constexpr bool CH = decltype(CHc)::value;
-    hipLaunchKernelGGL((agx::k_traj_append<NV, CH>), dim3((unsigned)((units + 63) / 64)), dim3(64), 0, o->copy_stream, o->d_model, o->d_ocp, L.sp, o->d_traj,
-                       o->d_pts, L.m, L.end, o->st_cap, o->st_span - 1);
-    HIPCHK(hipGetLastError());
-    return 0;
-  });
-  if (rc) return rc;
-  if (o->cost_wide)
-    HIPCHK((hipError_t)agx_cost_pairs_fill_ring_launch((void *)o->copy_stream, o->d_cw, L.sp.gw_item, o->d_traj, o->B, L.m, L.end, o->st_cap, o->st_span - 1,
-                                                       o->stride));
-  if (behind_solver && stream_time_mark(o, 1, o->copy_stream)) return -1;
-  return 0;
-}
-}  // namespace
-extern "C" {
-
-int agx_traj_stream_timing(agx_ocp *o, int enable, double *ms_sum, long long *count) {
-  if (!o) return fail("null handle");
-  if (set_device(o)) return -1;
-  // read out what has been recorded: both streams have to be through with it
-  if (o->st_tev_used[0] || o->st_tev_used[1]) {
-    HIPCHK(hipStreamSynchronize(o->stream));
-    if (o->copy_stream) HIPCHK(hipStreamSynchronize(o->copy_stream));
-    for (int kind = 0; kind < 2; ++kind) {
-      for (size_t k = 0; k + 1 < o->st_tev_used[kind]; k += 2) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, o->st_tev[kind][k], o->st_tev[kind][k + 1]));
-        o->st_tms[kind] += ms;
-        o->st_tn[kind] += 1;
-      }
-      o->st_tev_used[kind] = 0;
-    }
-  }
-  if (ms_sum && count)
-    for (int kind = 0; kind < 2; ++kind) { ms_sum[kind] = o->st_tms[kind]; count[kind] = o->st_tn[kind]; }
-  if ((enable != 0) != o->st_timing) {
-    o->st_timing = enable != 0;
-    for (int kind = 0; kind < 2; ++kind) { o->st_tms[kind] = 0.0; o->st_tn[kind] = 0; }
-  }
-  return 0;
-}
-
-int agx_traj_stream_append(agx_ocp *o, int m, const double *q, const double *dq, const double *ddq, const double *pose, const double *w_pose,
-                           const double *w_collision) {
-  if (!o || !q || !dq || !ddq) return fail("agx_traj_stream_append: null argument");
-  if (!o->streamed) return fail("agx_traj_stream_append: the handle has no streamed trajectory (agx_traj_stream_create)");
-  if (m < 1) return fail("agx_traj_stream_append: m must be at least 1");
-  if (m > INT_MAX - o->st_end) return fail("agx_traj_stream_append: end + m does not fit an int (logical sample indexes are int)");
-  if ((long long)o->st_end + m - o->st_first > o->st_cap)
-    return fail("agx_traj_stream_append: " + std::to_string(m) + " more samples overflow the ring, release the past first (first " + std::to_string(o->st_first) +
-                ", end " + std::to_string(o->st_end) + ", capacity " + std::to_string(o->st_cap) + ")");
-  const size_t B = o->B, nv = o->nv, nvu = o->nvu, np = B * (size_t)m;
-  struct { const double *a; size_t n; const char *name; } in[] = {{q, np * nvu, "q"}, {dq, np * nvu, "dq"}, {ddq, np * nvu, "ddq"}, {pose, np * 12, "pose"},
-                                                               {w_pose, np * 6, "w_pose"}, {w_collision, np, "w_collision"}};
-  for (const auto &c : in)
-    if (c.a)
-      for (size_t i = 0; i < c.n; ++i)
-        if (!std::isfinite(c.a[i])) return fail(std::string("agx_traj_stream_append: non-finite value in ") + c.name + " (element " + std::to_string(i) + ")");
-  if (set_device(o)) return -1;
-  // pieces of at most st_chunk samples, one staging buffer each
-  for (int j0 = 0; j0 < m; j0 += o->st_chunk) {
-    const int mp = std::min(o->st_chunk, m - j0);
-    const int i = o->st_next;
-    // the buffer's previous piece: its copy and its fill have to be over before the host rewrites the page-locked half and the
-    // copy stream the device half.  The fill is then complete for everybody: nothing is left to join.
-    if (o->st_used[i]) {
-      HIPCHK(hipEventSynchronize(o->ev_st[i]));
-      o->st_pending[i] = false;
-    }
-    const size_t npp = B * (size_t)mp, n = npp * nv;
-    double *h = o->st_host[i], *d = o->d_st_stage[i];
-    const double *src3[3] = {q, dq, ddq};
-    const bool whole = mp == m;  // one piece: the caller's [B][m] arrays have the layout of the chunk
-    for (int a = 0; a < 3; ++a) {
-      if (whole && !o->padded) { std::memcpy(h + a * n, src3[a], sizeof(double) * n); continue; }
-      for (size_t b = 0; b < B; ++b)
-        pad_rows(h + a * n + b * mp * nv, src3[a] + (b * m + j0) * nvu, (size_t)mp, 1, (int)nvu, (int)nv, 0.0);
-    }
-    size_t used = 3 * n;
-    agx::SineParams sp = o->st_sp;
-    sp.gq = d; sp.gdq = d + n; sp.gddq = d + 2 * n;
-    struct { const double *a; size_t w; const double **dst; } opt[] = {{pose, 12, &sp.gpose}, {w_pose, 6, &sp.gw_pose}, {w_collision, 1, &sp.gw_item}};
-    for (const auto &c : opt)
-      if (c.a) {
-        if (whole) std::memcpy(h + used, c.a, sizeof(double) * npp * c.w);
-        else
-          for (size_t b = 0; b < B; ++b) std::memcpy(h + used + b * mp * c.w, c.a + (b * m + j0) * c.w, sizeof(double) * mp * c.w);
-        *c.dst = d + used;
-        used += npp * c.w;
-      }
-    const int end = o->st_end;
-    o->st_last.buf = i; o->st_last.m = mp; o->st_last.end = end; o->st_last.used = used; o->st_last.sp = sp;
-    if (stream_enqueue_last(o, true)) return -1;
-    HIPCHK(hipEventRecord(o->ev_st[i], o->copy_stream));
-    o->st_used[i] = o->st_pending[i] = true;
-    o->st_lo[i] = end;
-    o->st_end = end + mp;
-    o->st_next = 1 - i;
-  }
-  return 0;
-}
-
-int agx_traj_stream_release(agx_ocp *o, int k) {
-  if (!o) return fail("null handle");
-  if (!o->streamed) return fail("agx_traj_stream_release: the handle has no streamed trajectory (agx_traj_stream_create)");
-  if (k < o->st_first || k > o->st_end)
-    return fail("agx_traj_stream_release: " + std::to_string(k) + " is outside [first, end] = [" + std::to_string(o->st_first) + ", " + std::to_string(o->st_end) + "]");
-  o->st_first = k;
-  return 0;
-}
-
-int agx_traj_stream_joins(agx_ocp *o, long long *joins, int *pending) {
-  if (!o) return fail("null handle");
-  if (!o->streamed) return fail("agx_traj_stream_joins: the handle has no streamed trajectory (agx_traj_stream_create)");
-  if (joins) *joins = o->st_joins;
-  if (pending) *pending = (o->st_pending[0] ? 1 : 0) + (o->st_pending[1] ? 1 : 0);
-  return 0;
-}
-
-int agx_traj_stream_range(agx_ocp *o, int *first, int *end) {
-  if (!o) return fail("null handle");
-  if (!o->streamed) return fail("agx_traj_stream_range: the handle has no streamed trajectory (agx_traj_stream_create)");
-  if (first) *first = o->st_first;
-  if (end) *end = o->st_end;
   return 0;
 }
 

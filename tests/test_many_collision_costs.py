@@ -319,6 +319,27 @@ def test_hip_resident_sine_trajectory_with_fourteen_pair_costs(hip_backend):
 
 
 @pytest.mark.gpu
+def test_hip_resident_cartesian_trajectory_fills_the_pair_rows(hip_backend):
+    """The Cartesian generator on a wide cost set: the pair rows of every sample hold [item weight | 1], as those of the sine
+    generator above.  Amplitude 0: every target is the initial pose, so the inverse kinematics has nothing to do."""
+    table = _chain()
+    T, n, n_points = 4, 14, 6
+    po, *_ = _problem(table, n, T=T)
+    h = hip_backend.HipOcp(table, po, B)
+    q0 = np.tile(np.array([0.1, -0.4, 0.3, -0.8, 0.2, 0.5]), (B, 1))
+    h.cartesian_sine_trajectory(n_points, 0.01, q0, np.zeros((B, 3)), np.ones((B, 3)), np.full(6, 1.0), np.full(6, 0.1), np.full(6, 1e-3),
+                                np.full(6, 2.0), table.frame_id("tool"))
+    tiles = np.stack([h.traj_tile(k) for k in range(n_points)], axis=1)
+    tiles_t = np.stack([h.traj_tile(k, terminal=True) for k in range(n_points)], axis=1)
+    for p in range(n):
+        o_r, o_t = po.running_offsets[3 + p], po.terminal_offsets[2 + p]
+        assert np.all(tiles[..., o_r] == 0.1) and np.all(tiles[..., o_r + 1] == 1.0)
+        assert np.all(tiles_t[..., o_t] == 0.1) and np.all(tiles_t[..., o_t + 1] == 1.0)
+    np.testing.assert_allclose(h.traj_point(n_points - 1)[0], q0, atol=1e-12)
+    h.close()
+
+
+@pytest.mark.gpu
 def test_hip_pair_costs_next_to_a_wide_constraint_set_match_the_checker(hip_backend):
     """14 pair costs next to a state box, torque limits and 12 pair constraints (wide constraint layout); the tolerances of
     test_many_collision_pairs.py::_assert_matches_checker."""
