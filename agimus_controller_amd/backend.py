@@ -18,6 +18,10 @@ from . import _abi
 
 _CSRC = pathlib.Path(__file__).resolve().parent / "csrc"
 LIB_PATH = pathlib.Path(os.environ.get("AGX_LIB", _CSRC / "libagimus_hip.so"))  # AGX_LIB: development override
+# The same library with the launch sites of the general-row kernels of large models compiled out (-DAGX_NO_GENERAL_ROWS on the
+# unit of the capacities 16 / 30 / 32): built next to the product by the split build, loaded only by the test that compares a
+# handle without general rows against it bit for bit (AGX_LIB in a child process).
+NOGEN_LIB_PATH = _CSRC / "libagimus_hip_nogen.so"
 _LIB = None
 
 # Every symbol include/agimus_hip.h declares (checked by the CPU test-suite).
@@ -37,7 +41,7 @@ EXPORTED_SYMBOLS = [
     "agx_traj_stream_create", "agx_traj_stream_append", "agx_traj_stream_release", "agx_traj_stream_range",
     "agx_traj_stream_joins", "agx_traj_stream_timing", "agx_ocp_set_obstacle_placements",
     "agx_ocp_set_first_pack", "agx_ocp_first_pack_counts", "agx_ocp_handoff_counts",
-    "agx_ocp_iter_log", "agx_ocp_iter_log_read", "agx_ocp_item_costs", "agx_ocp_carry_counts",
+    "agx_ocp_iter_log", "agx_ocp_iter_log_read", "agx_ocp_item_costs", "agx_ocp_carry_counts", "agx_ocp_general_rows",
 ]  # fmt: skip
 
 
@@ -60,13 +64,16 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
     hdr = _CSRC.parent.parent / "include" / "agimus_hip.h"
     pairs_src = _CSRC / "agx_cost_pairs.hip"  # the wide-cost-set kernels: a translation unit of their own (see the file)
     diag_src = _CSRC / "agx_diag.hip"  # the diagnostics kernels (iteration log, per-item costs): likewise, one unit for every capacity
-    srcs = [_CSRC / "agimus_hip.hip"] + sorted(_CSRC.glob("*.hpp")) + [hdr, _CSRC / "agx_front.py", pairs_src, diag_src]
-    if not force and LIB_PATH.exists() and LIB_PATH.stat().st_mtime >= max(s.stat().st_mtime for s in srcs):
+    gen_src = _CSRC / "agx_general_rows.hip"  # the general cost rows of large models: likewise, the capacities of group 1
+    srcs = [_CSRC / "agimus_hip.hip"] + sorted(_CSRC.glob("*.hpp")) + [hdr, _CSRC / "agx_front.py", pairs_src, diag_src, gen_src]
+    split = os.environ.get("AGX_BUILD_SPLIT", "1") != "0"
+    newest = max(s.stat().st_mtime for s in srcs)
+    if not force and all(p.exists() and p.stat().st_mtime >= newest for p in ([LIB_PATH, NOGEN_LIB_PATH] if split else [LIB_PATH])):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
-    if os.environ.get("AGX_BUILD_SPLIT", "1") == "0":
-        _run(base + [f"-I{hdr.parent}", "-shared", "-o", str(LIB_PATH), str(srcs[0]), str(pairs_src), str(diag_src)], verbose)
+    if not split:
+        _run(base + [f"-I{hdr.parent}", "-shared", "-o", str(LIB_PATH), str(srcs[0]), str(pairs_src), str(diag_src), str(gen_src)], verbose)
         return LIB_PATH
     import importlib.util
 
@@ -80,9 +87,14 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
     for g in front.GROUPS:
         cmd = base + ["-c", f"-I{hdr.parent}"] + front.rename_flags(names, g) + ["-o", str(obj / f"agx_g{g}.o"), str(srcs[0])]
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
+    g1 = max(front.GROUPS)  # the unit of the large capacities once more, without the launch sites of the general-row kernels
+    cmd = base + ["-c", f"-I{hdr.parent}", "-DAGX_NO_GENERAL_ROWS"] + front.rename_flags(names, g1) + ["-o", str(obj / f"agx_g{g1}_nogen.o"), str(srcs[0])]
+    procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
     cmd = base + ["-c", f"-I{hdr.parent}", "-DAGX_GROUP=0", "-o", str(obj / "agx_cost_pairs.o"), str(pairs_src)]  # the sizes of group 0
     procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
     cmd = base + ["-c", f"-I{hdr.parent}", "-o", str(obj / "agx_diag.o"), str(diag_src)]
+    procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
+    cmd = base + ["-c", f"-I{hdr.parent}", "-DAGX_GROUP=1", "-o", str(obj / "agx_general_rows.o"), str(gen_src)]  # the sizes of group 1
     procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
     (obj / "agx_front.cpp").write_text(front.front_source(hdr.read_text()))
     _run(["g++", "-O2", "-std=c++17", "-fPIC", f"-I{hdr.parent}", "-c", "-o", str(obj / "agx_front.o"), str(obj / "agx_front.cpp")], verbose)
@@ -96,7 +108,10 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
     if failed:
         raise failed
     _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB_PATH)] + [str(obj / f"agx_g{g}.o") for g in front.GROUPS]
-         + [str(obj / "agx_cost_pairs.o"), str(obj / "agx_diag.o"), str(obj / "agx_front.o")], verbose)
+         + [str(obj / "agx_cost_pairs.o"), str(obj / "agx_diag.o"), str(obj / "agx_general_rows.o"), str(obj / "agx_front.o")], verbose)
+    _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(NOGEN_LIB_PATH)]
+         + [str(obj / (f"agx_g{g}_nogen.o" if g == g1 else f"agx_g{g}.o")) for g in front.GROUPS]
+         + [str(obj / "agx_cost_pairs.o"), str(obj / "agx_diag.o"), str(obj / "agx_general_rows.o"), str(obj / "agx_front.o")], verbose)
     return LIB_PATH
 
 
@@ -201,6 +216,12 @@ class HipOcp:
     def cost_wide(self) -> bool:
         """The handle runs a wide cost set (agx_ocp_cost_wide): set_refs then takes no frame-id table."""
         return lib().agx_ocp_cost_wide(self._h) == 1
+
+    @property
+    def general_rows(self) -> bool:
+        """The handle has an active ControlGrav / FrameVelocity cost row (agx_ocp_general_rows): the kernels that carry Lxu and
+        the dense Lxx blocks run."""
+        return lib().agx_ocp_general_rows(self._h) == 1
 
     def close(self):
         if getattr(self, "_h", None):

@@ -30,6 +30,21 @@ extern "C" int agx_diag_iter_log_launch(void *stream, const DevState *st, int B,
 extern "C" int agx_diag_item_costs_launch(void *stream, int nv, int chain, const DevModel *m, const DevRows *rows2, int B, int T, const double *xs,
                                           const double *us, const RefView *rv, int R, double *cost, double *Lx, double *Lu, const void *obs);
 
+// launchers of the general-cost-row kernels of large models, likewise (agx_general_rows.hip; dest: the constants below)
+extern "C" int agx_general_rows_launch(int dest, void *stream, int nv, int prismatic, long long units, const DevModel *m, const DevOcp *o,
+                                       const double *dts, const double *xs, const double *us, const RefView *rv, double *out0, double *out1,
+                                       double *out2, const DevState *st, int phase, int only, int R);
+extern "C" int agx_general_kkt_launch(void *stream, int nv, long long nodes, const DevOcp *o, const double *qts, const double *auxs, const double *auxg,
+                                      const double *dxs, const double *wss, double *dus, double *nodestat, const DevState *st);
+constexpr int kGenToQp = 0, kGenToCanonical = 1, kGenItems = 2;  // agx_general_rows.hpp
+// -DAGX_NO_GENERAL_ROWS compiles the launch sites of these kernels out (and K1 of large models reads d_ocp, as it did before
+// they existed): the second library of backend.build(), against which a test compares a handle without general rows bit for bit.
+#ifdef AGX_NO_GENERAL_ROWS
+constexpr bool kGeneralRowsWg = false;
+#else
+constexpr bool kGeneralRowsWg = true;
+#endif
+
 #include "agx_host_handle.hpp"
 
 namespace {
@@ -291,7 +306,7 @@ int launch_calc_diff_rows(agx_ocp *o, bool masked, bool running_only) {
 // K1 production: QP tiles in acceleration-input form.  Serial chains use the 8-lanes-per-node
 // kernel (agx_k1_lanes.hpp); trees fall back to one lane per node.
 // phase 1: the pass runs at the trial iterates (staging halves of xs / us) of the instances in the line search and leaves
-// their tiles in place of the current ones (k_sqp_head / k_sqp_accept, agx_kernels.hpp); nv <= 7 only.
+// their tiles in place of the current ones (k_sqp_head / k_sqp_accept, agx_kernels.hpp); every model size.
 // compact (phase 0, eight-lane kernel): every instance inherits its tiles (DevState::carry): a grid over nodes 0, T - 1 and T only.
 int launch_k1(agx_ocp *o, bool running_only, bool term_only, int phase, bool compact) {
   return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
@@ -304,7 +319,7 @@ int launch_k1(agx_ocp *o, bool running_only, bool term_only, int phase, bool com
       // large models: one workgroup per node, running and terminal nodes in one launch (agx_big_k1.hpp)
       if (term_only) return 0;  // the launch of the running nodes (profiled path) already covered the terminal ones
       launch_wg(o, [&](auto PRc) {
-        hipLaunchKernelGGL((agx::k_calc_qp_wg<NV, decltype(PRc)::value>), dim3((int)(units + o->B)), dim3(256), 0, o->stream, o->d_model, o->d_ocp, o->d_dt, xs_in,
+        hipLaunchKernelGGL((agx::k_calc_qp_wg<NV, decltype(PRc)::value>), dim3((int)(units + o->B)), dim3(256), 0, o->stream, o->d_model, kGeneralRowsWg ? o->d_ocp_k1 : o->d_ocp, o->d_dt, xs_in,
                          us_in, o->rv, o->d_qt, o->d_aux, o->d_state, phase);
       });
     } else if (NV <= 7 && !o->general && CH && o->k1_lanes && o->lanes_ok) {
@@ -362,6 +377,11 @@ int launch_cost_pairs(agx_ocp *o, int dest, int sel, int phase, bool masked = fa
 
 int launch_calc_diff(agx_ocp *o, bool masked, bool running_only = false) {
   if (launch_calc_diff_rows(o, masked, running_only)) return -1;
+  if (kGeneralRowsWg && o->general && o->nv > 7) {  // large models: k_general_rows_wg adds the ControlGrav / FrameVelocity rows (Lxu, dense Lxx) behind k_calc_diff
+    const long long units = (long long)o->B * o->T + (running_only ? 0 : o->B);
+    HIPCHK((hipError_t)agx_general_rows_launch(kGenToCanonical, (void *)o->stream, o->nv, o->hm.prismatic ? 1 : 0, units, o->d_model, o->d_ocp, o->d_dt,
+                                               o->d_xs, o->d_us, &o->rv, o->d_tiles, nullptr, nullptr, masked ? o->d_state : nullptr, 0, -1, 0));
+  }
   return o->cost_wide ? launch_cost_pairs(o, agx::kPairsToCanonical, running_only ? 1 : 0, 0, masked) : 0;
 }
 
@@ -369,6 +389,14 @@ int launch_calc_diff(agx_ocp *o, bool masked, bool running_only = false) {
 // phase and nodes.
 int launch_calc_qp(agx_ocp *o, bool running_only = false, bool term_only = false, int phase = 0, bool compact = false) {
   if (launch_k1(o, running_only, term_only, phase, compact)) return -1;
+  if (kGeneralRowsWg && o->general && o->nv > 7 && !term_only) {
+    // large models: k_general_rows_wg adds the ControlGrav / FrameVelocity rows into the tiles of the K1 launch in front of it,
+    // which covers every node (launch_k1), at the same iterate (phase 1: the trial points) and by the same predicate
+    const double *xs_in = phase ? o->d_xs + (size_t)o->B * (o->T + 1) * o->nx : o->d_xs;
+    const double *us_in = phase ? o->d_us + (size_t)o->B * o->T * o->nu : o->d_us;
+    HIPCHK((hipError_t)agx_general_rows_launch(kGenToQp, (void *)o->stream, o->nv, o->hm.prismatic ? 1 : 0, (long long)o->B * (o->T + 1), o->d_model,
+                                               o->d_ocp, o->d_dt, xs_in, us_in, &o->rv, o->d_qt, o->d_aux, o->d_auxg, o->d_state, phase, -1, 0));
+  }
   return o->cost_wide ? launch_cost_pairs(o, agx::kPairsToQp, running_only ? 1 : (term_only ? 2 : 0), phase) : 0;
 }
 
@@ -466,7 +494,10 @@ int launch_step(agx_ocp *o, int iter, int max_iter, int mode, bool with_node_kkt
         else
           hipLaunchKernelGGL((agx::k_node_kkt<NV>), dim3((int)((nodes * 8 + 255) / 256)), dim3(256), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
                              o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
-      } else
+      } else if (kGeneralRowsWg && o->general)  // every block of the identities (k_node_kkt_big_gen, agx_general_rows.hpp)
+        HIPCHK((hipError_t)agx_general_kkt_launch((void *)o->stream, NV, nodes, o->d_ocp, o->d_qt, o->d_aux, o->d_auxg, o->d_dx, o->d_w, o->d_du,
+                                                  o->d_nodestat, o->d_state));
+      else
         hipLaunchKernelGGL((agx::k_node_kkt_big<NV>), dim3((int)((nodes + 1) / 2)), dim3(64), 0, o->stream, o->d_ocp, o->d_qt, o->d_aux,
                            o->d_dx, o->d_w, o->d_du, o->d_nodestat, o->d_state);
     }
@@ -1192,7 +1223,6 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
       case AGX_RES_STATE: case AGX_RES_CONTROL: case AGX_RES_FRAME_PLACEMENT: case AGX_RES_FRAME_TRANSLATION: case AGX_RES_FRAME_ROTATION:
       case AGX_RES_COLLISION: break;
       case AGX_RES_CONTROL_GRAV: case AGX_RES_FRAME_VELOCITY:
-        if (m->h.nv > 7) return fail("agx_ocp_create: ControlGrav / FrameVelocity rows are implemented for nv <= 7");
         if (row.kind == AGX_RES_FRAME_VELOCITY && (row.frame < 0 || row.frame >= m->h.nframes || row.frame_b < 0 || row.frame_b > 2))
           return fail("agx_ocp_create: FrameVelocity row needs a valid frame and a reference frame 0 (WORLD), 1 (LOCAL) or 2 (LOCAL_WORLD_ALIGNED)");
         break;
@@ -1327,11 +1357,19 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   o->ho.eps_rel = d->eps_rel;
   o->ho.use_filter = d->use_filter_line_search ? 1 : 0;
   // (the filter test lives in k_sqp_accept, which serves every model size and every kind of cost row)
+  if (!kGeneralRowsWg && o->general && o->nv > 7)
+    return bail("agx_ocp_create: this build has the ControlGrav / FrameVelocity kernels of models above 7 joints compiled out (AGX_NO_GENERAL_ROWS)");
   if (o->has_con && o->nv > 7) {  // large models: ConstraintModelControlLimit only (agx_big.hpp)
     for (int lay = 0; lay < 2; ++lay)
       for (int r = 0; r < o->ho.cons[lay].n; ++r)
         if (o->ho.cons[lay].kind[r] == AGX_RES_FRAME_VELOCITY || o->ho.cons[lay].kind[r] == AGX_RES_CONTROL_GRAV)
           return bail("agx_ocp_create: FrameVelocity / ControlGrav constraints are implemented for models of at most 7 joints (after padding)");
+    // general cost rows next to constraints: k_admm_update_big does not carry the blocks Lqv | Lvvd | Lqu
+    for (int lay = 0; lay < 2; ++lay)
+      for (int r = 0; r < o->ho.rows[lay].n; ++r)
+        if (o->ho.rows[lay].active[r] && (o->ho.rows[lay].kind[r] == AGX_RES_CONTROL_GRAV || o->ho.rows[lay].kind[r] == AGX_RES_FRAME_VELOCITY))
+          return bail(std::string("agx_ocp_create: a ") + (o->ho.rows[lay].kind[r] == AGX_RES_CONTROL_GRAV ? "ControlGrav" : "FrameVelocity") +
+                      " cost row together with constraints is implemented for models of at most 7 joints (after padding)");
   }
   {
     auto n_frame_rows = [](const DevRows &r) {
@@ -1360,6 +1398,7 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
     o->lanes_ok = k1_stride <= agx::kLjRef && n_frame_rows(o->ho.rows[0]) <= 2 && n_frame_rows(o->ho.rows[1]) <= 2 &&
                   n_collision_rows(o->ho.rows[0]) <= 1 && n_collision_rows(o->ho.rows[1]) <= 1 && !o->general && !n_vector_exp_rows();
   }
+  int wg_k1_stride = 0;  // large models with general rows: the tile doubles K1 stages
   if (o->nv > 8) {
     // the workgroup-per-node kernels stage the reference tile and the dense residual rows of a node in LDS
     auto n_dense = [](const DevRows &r) {
@@ -1369,7 +1408,24 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
           n += r.kind[i] == AGX_RES_FRAME_PLACEMENT ? 6 : ((r.kind[i] == AGX_RES_FRAME_TRANSLATION || r.kind[i] == AGX_RES_FRAME_ROTATION) ? 3 : (r.kind[i] == AGX_RES_COLLISION ? 1 : 0));
       return n;
     };
-    if (o->stride > agx::kWgRef) return bail("agx_ocp_create: reference tile of " + std::to_string(o->stride) + " doubles per node exceeds the large-model limit of " + std::to_string(agx::kWgRef));
+    // A handle with general rows: K1 stages the tile up to the end of its last row that is not a general row (it skips the two
+    // kinds), k_general_rows_wg from the first general row on (agx_general_rows.hpp: general_ref_lo); the limit applies to the
+    // caller's tile and to either piece.  A padded 31-joint model keeps the five-row set of a torque-controlled arm that way.
+    // (wg_costs of K1 still forms the tile pointer of every active row and loads its item weight before it looks at the kind:
+    // for a general row that is a load from LDS K1 has not staged -- at most 258 doubles into WgNode's ref | J region, inside
+    // the structure -- whose value is never used.  K1 uses nothing of a general row's tile; it does touch that one address.)
+    int gen_lo = o->stride;
+    if (o->general) {
+      wg_k1_stride = 1;
+      for (int lay = 0; lay < 2; ++lay)
+        for (int r = 0; r < o->ho.rows[lay].n; ++r) {
+          const DevRows &R = o->ho.rows[lay];
+          if (R.kind[r] == AGX_RES_CONTROL_GRAV || R.kind[r] == AGX_RES_FRAME_VELOCITY) gen_lo = std::min(gen_lo, R.off[r]);
+          else wg_k1_stride = std::max(wg_k1_stride, R.off[r] + 1 + R.nref[r] + R.nr[r]);
+        }
+    }
+    const int widest = o->general ? std::max(o->stride_u, std::max(wg_k1_stride, o->stride - gen_lo)) : o->stride;
+    if (widest > agx::kWgRef) return bail("agx_ocp_create: reference tile of " + std::to_string(widest) + " doubles per node exceeds the large-model limit of " + std::to_string(agx::kWgRef));
     if (n_dense(o->ho.rows[0]) > agx::kWgJ || n_dense(o->ho.rows[1]) > agx::kWgJ) return bail("agx_ocp_create: more than 16 frame / collision residual components per node (large models)");
   }
   // two-level sweep for small batches of unconstrained problems on the MFMA-layout kernel.  Only with Gauss-Newton Hessians of
@@ -1406,7 +1462,7 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
   hipError_t bad = hipSuccess;
   auto alloc = [&](auto **field, size_t count) { if (bad == hipSuccess) bad = o->own.device(field, count, true); };
   alloc(&o->d_model, 1);
-  alloc(&o->d_ocp, o->cost_wide ? 2 : 1);  // wide cost sets: [1] the copy K1 reads
+  alloc(&o->d_ocp, (o->cost_wide || wg_k1_stride) ? 2 : 1);  // wide cost sets, general rows of large models: [1] the copy K1 reads
   if (o->cost_wide) alloc(&o->d_cw, 1);
   alloc(&o->d_dt, T);
   alloc(&o->d_xs, 2 * B * (T + 1) * nx);  // second half: shift staging
@@ -1430,7 +1486,7 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
       if (o->dt[t] != o->dt[0]) o->shift_nodes.push_back(t);
     if (!o->shift_nodes.empty()) alloc(&o->d_shift_nodes, o->shift_nodes.size());
   }
-  if (o->general) alloc(&o->d_auxg, B * (T + 1) * (size_t)(3 * o->nv * 8));
+  if (o->general) alloc(&o->d_auxg, B * (T + 1) * (size_t)(3 * o->nv * ld));  // 3 A::B2 of the capacity
   if (o->has_con) {
     alloc(&o->d_qt2, B * (T + 1) * (size_t)o->qt_size);
     const size_t cs = (size_t)o->con_cs;  // AGX_MAX_NC, wide sets: their own stride
@@ -1458,9 +1514,9 @@ int agx_ocp_create(const agx_model *m, const agx_ocp_desc *d, int batch, int dev
       (o->cost_wide && hipMemcpy(o->d_cw, &o->hw, sizeof(DevCostWide), hipMemcpyHostToDevice) != hipSuccess) ||
       hipMemcpy(o->d_dt, o->dt.data(), sizeof(double) * T, hipMemcpyHostToDevice) != hipSuccess)
     return bail("agx_ocp_create: upload of the problem description failed");
-  if (o->cost_wide) {
+  if (o->cost_wide || wg_k1_stride) {
     DevOcp k1 = o->ho;
-    k1.stride = std::max(1, std::max(o->hw.lay[0].prefix, o->hw.lay[1].prefix));
+    k1.stride = wg_k1_stride ? wg_k1_stride : std::max(1, std::max(o->hw.lay[0].prefix, o->hw.lay[1].prefix));
     o->d_ocp_k1 = o->d_ocp + 1;
     if (hipMemcpy(o->d_ocp_k1, &k1, sizeof(DevOcp), hipMemcpyHostToDevice) != hipSuccess) return bail("agx_ocp_create: upload of the problem description failed");
   }
@@ -1537,6 +1593,11 @@ int agx_ocp_set_geom_placement(agx_ocp *o, int frame, const double *se3) {
                         sizeof(double) * 12, hipMemcpyHostToDevice, o->stream));
   HIPCHK(hipStreamSynchronize(o->stream));
   return 0;
+}
+
+int agx_ocp_general_rows(agx_ocp *o) {
+  if (!o) return fail("null handle");
+  return o->general ? 1 : 0;
 }
 
 int agx_ocp_cost_wide(agx_ocp *o) {
@@ -2042,6 +2103,17 @@ int agx_ocp_item_costs(agx_ocp *o, double *cost_r, double *Lx_r, double *Lu_r, d
                                             d_Lu, o->obs_set ? o->d_obs : nullptr);
   if (rc < 0) return fail("agx_ocp_item_costs: no kernel instantiation for nv = " + std::to_string(NV));
   HIPCHK((hipError_t)rc);
+  if (kGeneralRowsWg && o->general && NV > 7)  // large models: the ControlGrav / FrameVelocity rows, one launch each (k_item_costs leaves them out)
+    for (int lay = 0; lay < 2; ++lay)
+      for (int r = 0; r < o->ho.rows[lay].n; ++r) {
+        const int kind = o->ho.rows[lay].kind[r];
+        if (!o->ho.rows[lay].active[r] || (kind != AGX_RES_CONTROL_GRAV && kind != AGX_RES_FRAME_VELOCITY)) continue;
+        bool other = false;  // the other table's row r is evaluated by the same launch
+        if (lay == 1 && r < o->ho.rows[0].n && o->ho.rows[0].active[r]) other = o->ho.rows[0].kind[r] == AGX_RES_CONTROL_GRAV || o->ho.rows[0].kind[r] == AGX_RES_FRAME_VELOCITY;
+        if (other) continue;
+        HIPCHK((hipError_t)agx_general_rows_launch(kGenItems, (void *)o->stream, NV, o->hm.prismatic ? 1 : 0, (long long)B * (T + 1), o->d_model, o->d_ocp,
+                                                   o->d_dt, o->d_xs, o->d_us, &o->rv, d_cost, d_Lx, d_Lu, nullptr, 0, r, R));
+      }
   if (o->cost_wide)  // the pair rows of a wide cost set: each pair's own value and gradient row
     HIPCHK((hipError_t)agx_cost_pairs_launch(agx::kPairsItems, (void *)o->stream, (long long)B * (T + 1), o->d_model, o->d_ocp, o->d_cw, o->d_dt, o->d_xs,
                                              &o->rv, d_cost, d_Lx, nullptr, 0, 0, R, o->obs_set ? o->d_obs : nullptr));

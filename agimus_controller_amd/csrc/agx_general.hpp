@@ -9,6 +9,8 @@
 //
 // Problems with such rows run on the one-lane-per-node kernels instantiated with GEN = true
 // (correctness path, nv <= 7); the extra Hessian blocks travel in CostGen next to CostAcc.
+// Large models (capacities 16 / 30 / 32): agx_general_rows.hpp restates this arithmetic for the
+// workgroup-per-node path (k_general_rows_wg behind k_calc_qp_wg, k_node_kkt_big_gen).
 //
 // (included by agx_device.hpp users after node_costs is defined)
 #pragma once

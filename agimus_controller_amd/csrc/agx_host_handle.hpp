@@ -115,8 +115,9 @@ struct agx_ocp {
   bool has_con = false;
   std::vector<int> shift_nodes;  // large models: nodes with dt_i != dt_0 (integrated by the warm-start shift)
   int *d_shift_nodes = nullptr;
-  bool general = false;       // ControlGrav / FrameVelocity cost rows: one-lane GEN kernels (agx_general.hpp)
-  double *d_auxg = nullptr;   // [B][T+1][3 nv 8]: Lqv | Lvvd | Lqu of every node (general problems)
+  bool general = false;       // ControlGrav / FrameVelocity cost rows: one-lane GEN kernels (agx_general.hpp) up to 7 joints,
+                              // k_general_rows_wg / k_node_kkt_big_gen behind the workgroup kernels above (agx_general_rows.hpp)
+  double *d_auxg = nullptr;   // [B][T+1][3 nv LD]: Lqv | Lvvd | Lqu of every node (general problems; LD: the tiles' row stride)
   double *d_qt2 = nullptr, *d_cg = nullptr, *d_cjac = nullptr, *d_y = nullptr, *d_z = nullptr, *d_cx = nullptr, *d_admmstat = nullptr,
          *d_fac = nullptr,  // Riccati factors of every node for the gradient-only ADMM sweeps [B][T][192]
          *d_segP = nullptr;  // closed-loop transition products of the horizon segments [B][kSeg][4][64] (agx_admm.hpp)
@@ -131,7 +132,8 @@ struct agx_ocp {
   bool cost_wide = false;
   DevCostWide hw{};
   DevCostWide *d_cw = nullptr;
-  DevOcp *d_ocp_k1 = nullptr;  // == d_ocp unless cost_wide, then d_ocp + 1: a view, never registered
+  DevOcp *d_ocp_k1 = nullptr;  // == d_ocp unless cost_wide (or general rows on a large model: K1 stages the tile up to its last
+                               // row that is not a general row), then d_ocp + 1: a view, never registered
   int n_rows_all[2] = {0, 0};  // rows of the caller's tables, running / terminal (ho.rows[l].n + hw.lay[l].n)
   bool speculate = true;  // AGX_SPECULATE_GAINS=0: gains sweep only on exit
   bool gains_mfma = true; // AGX_GAINS_MFMA=0: scalar K = M Kw - taux for large models

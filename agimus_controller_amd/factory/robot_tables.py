@@ -305,6 +305,24 @@ def _random_body(rng, mass_range=(0.5, 4.0), size=0.15):
     return m, c, Q @ Ib @ Q.T
 
 
+def panda_fingers_table(armature=0.1) -> RobotTable:
+    """The Panda with two more REVOLUTE joints at the hand (the finger joints robot_model.py locks by default, as a seeded
+    two-joint chain): a serial chain of 9 that runs at the 16-joint capacity.  panda_gripper_table is the prismatic gripper."""
+    import dataclasses
+
+    p, f = panda_table(armature), chain_table(2, seed=5, armature=armature)
+
+    def cat(a, b):
+        return np.concatenate([np.asarray(a), np.asarray(b)])
+
+    return dataclasses.replace(
+        p, name="panda_fingers", joint_names=list(p.joint_names) + ["finger_joint1", "finger_joint2"], parent=np.arange(-1, 8, dtype=np.int32),
+        placement=cat(p.placement, f.placement), axis=cat(p.axis, f.axis), mass=cat(p.mass, 0.05 * f.mass), com=cat(p.com, 0.2 * f.com),
+        inertia=cat(p.inertia, 1e-3 * f.inertia), armature=cat(p.armature, f.armature), effort_limit=cat(p.effort_limit, [20.0, 20.0]),
+        lower_position_limit=cat(p.lower_position_limit, [-0.5, -0.5]), upper_position_limit=cat(p.upper_position_limit, [0.5, 0.5]),
+        velocity_limit=cat(p.velocity_limit, [1.0, 1.0]), frame_parent=np.asarray(p.frame_parent).copy())
+
+
 def chain_table(nv: int, seed: int = 0, armature=0.1, name=None) -> RobotTable:
     """Seeded serial chain with random placements/axes (test model)."""
     rng = np.random.default_rng(seed)

@@ -30,6 +30,22 @@ def goal_reaching_rows(frame: int):
     return running, terminal
 
 
+def general_rows(frame: int, ref_frame: int = 0, with_grav: bool = True, with_placement: bool = True):
+    """Row tables with the two general rows (ResidualModelControlGrav, ResidualModelFrameVelocity; ocp_croco_generic.py:186-194,
+    360-432) next to the goal-reaching rows: running Control, State, [FramePlacement], FrameVelocity, [ControlGrav]; terminal
+    State, FrameVelocity.  ref_frame: 0 WORLD, 1 LOCAL, 2 LOCAL_WORLD_ALIGNED.  At 32 joints the reference tile of the five
+    running rows exceeds the large-model limit: with_placement=False leaves the placement row out."""
+    running = [_abi.RowSpec(_abi.RES_CONTROL, name="control_reg"), _abi.RowSpec(_abi.RES_STATE, name="state_reg")]
+    if with_placement:
+        running.append(_abi.RowSpec(_abi.RES_FRAME_PLACEMENT, frame=frame, name="goal_tracking"))
+    running.append(_abi.RowSpec(_abi.RES_FRAME_VELOCITY, frame=frame, frame_b=ref_frame, name="ee_velocity"))
+    if with_grav:
+        running.append(_abi.RowSpec(_abi.RES_CONTROL_GRAV, name="ctrl_grav"))
+    terminal = [_abi.RowSpec(_abi.RES_STATE, name="state_reg"),
+                _abi.RowSpec(_abi.RES_FRAME_VELOCITY, frame=frame, frame_b=ref_frame, name="ee_velocity")]
+    return running, terminal
+
+
 def regulation_rows(terminal_weight: float = 1.0):
     """Row tables of the pick-and-place example's ocp_definition_file.yaml
     (control_reg + state_reg; terminal state_reg)."""

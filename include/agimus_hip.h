@@ -65,6 +65,10 @@ enum agx_activation_kind {
 };
 /* Exp / QuadExp: any residual but ControlGrav / FrameVelocity; |r| over the nr components of the row, diagonal second
  * derivative; the activation weights of the row's tile are ignored.  Forms recalled, parity against colmpc unpinned. */
+/* ControlGrav / FrameVelocity cost rows (the rows with Lxu and dense Lxx blocks) are accepted at every capacity.  Up to 7
+ * joints the one-lane-per-node kernels evaluate them; above (capacities 16 / 30 / 32) k_general_rows_wg adds them into the
+ * tiles of the workgroup-per-node derivative pass and k_node_kkt_big_gen forms the KKT shares (agx_ocp_general_rows tells).
+ * Above 7 joints such a cost row is refused together with any constraint.                                                 */
 
 /* One CostModelSumItem (ocp_croco_generic.py:578-585) lowered to a table row.
  * Per-node data of the row lives in the reference tile (agx_ocp_set_refs):
@@ -94,7 +98,8 @@ typedef struct agx_cost_row {
  * placement / velocity 6, ControlGrav nv) per node type; residuals on u are
  * dropped at the terminal node.  Models above 7 joints (after padding to the compiled
  * capacity): State, Control, collision and frame translation / rotation / placement
- * rows, up to 104 components per node; FrameVelocity / ControlGrav rows are refused. */
+ * rows, up to 104 components per node; FrameVelocity / ControlGrav constraint rows are refused, and so is any constraint
+ * next to a FrameVelocity / ControlGrav cost row. */
 typedef struct agx_constraint_row {
   int32_t kind;        /* agx_residual_kind                                     */
   int32_t active;      /* ConstraintListItem.active                             */
@@ -241,6 +246,9 @@ int agx_ocp_set_refs(agx_ocp *ocp, const double *ref_tile, const int32_t *frame_
  * qualifies), 0 otherwise.  On such a handle agx_ocp_set_refs, agx_ocp_set_refs_async and agx_ocp_set_refs_device refuse a
  * non-NULL frame-id table: every frame row looks at the frame of its agx_cost_row on every node.                           */
 int agx_ocp_cost_wide(agx_ocp *ocp);
+/* 1 when an active cost row of the handle is a ControlGrav or FrameVelocity row (the kernels that carry Lxu and the dense Lxx
+ * blocks run: the GEN one-lane kernels up to 7 joints, k_general_rows_wg / k_node_kkt_big_gen above), 0 otherwise.       */
+int agx_ocp_general_rows(agx_ocp *ocp);
 /* The same update without stalling the caller or the solver (the reference pays ~ T x #costs binding calls per step for it,
  * ocp_croco_generic.py:883-888), in two halves so that the tile of step k+1 can travel while step k is being solved:
  *   agx_ocp_set_refs_async  STAGES a tile: a second stream copies it into the handle's second device tile (the solver
