@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "agx_traj_stream_joins", "agx_traj_stream_timing", "agx_ocp_set_obstacle_placements",
     "agx_ocp_set_first_pack", "agx_ocp_first_pack_counts", "agx_ocp_handoff_counts",
     "agx_ocp_iter_log", "agx_ocp_iter_log_read", "agx_ocp_item_costs", "agx_ocp_carry_counts", "agx_ocp_general_rows",
+    "agx_ocp_clearance",
 ]  # fmt: skip
 
 
@@ -449,6 +450,45 @@ class HipOcp:
                "Lu_r": np.empty((self.B, self.T, Rr, self.nu)), "cost_t": np.empty((self.B, Rt)), "Lx_t": np.empty((self.B, Rt, self.nx))}  # fmt: skip
         _chk(lib().agx_ocp_item_costs(self._h, _p(out["cost_r"]), _p(out["Lx_r"]), _p(out["Lu_r"]), _p(out["cost_t"]), _p(out["Lx_t"])))
         return out
+
+    def clearance(self, pairs, q=None, witness=False, minimum=False):
+        """Signed distances of the geometry pairs `pairs` (agx_ocp_clearance): a sequence of (frame_a, frame_b), frame ids or names of
+        the table -- any pairs, rows of the problem or not.  q [B, m, nv]: the configurations; None: the resident iterate, m = T + 1
+        samples, terminal node included.  Returns dist [B, m, n]; with witness=True also [B, m, n, 3, 3] (point on a, point on b,
+        unit normal n, world frame, the points on the surfaces: pa - pb = dist n); with minimum=True also (min_dist [B],
+        min_where [B, 2]: sample and pair, the first of equal ones).  In that order, as a tuple when more than dist is asked for.
+        World-fixed frames stand where the solve sees them (set_geom_placement, set_obstacle_placements).  The call only reads."""
+        names = self.table.frame_names
+
+        def frame(f):
+            if isinstance(f, str):
+                if f not in names:
+                    raise ValueError(f"pairs: the table has no frame {f!r}")
+                return names.index(f)
+            return int(f)
+
+        try:
+            ids = [[frame(f) for f in pair] for pair in pairs]
+        except TypeError:
+            raise ValueError("pairs: expected a sequence of (frame_a, frame_b)") from None
+        n = len(ids)
+        if n < 1 or any(len(pair) != 2 for pair in ids):
+            raise ValueError("pairs: expected at least one (frame_a, frame_b)")
+        fr = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).T)
+        if q is None:
+            m = self.T + 1
+        else:
+            q = np.ascontiguousarray(np.asarray(q, dtype=np.float64))
+            if q.ndim != 3 or q.shape[0] != self.B or q.shape[1] < 1 or q.shape[2] != self.nv:
+                raise ValueError(f"q: expected shape ({self.B}, m, {self.nv}) with m >= 1, got {q.shape}")
+            m = q.shape[1]
+        dist = np.empty((self.B, m, n))
+        wit = np.empty((self.B, m, n, 3, 3)) if witness else None
+        dmin = np.empty(self.B) if minimum else None
+        where = np.empty((self.B, 2), dtype=np.int32) if minimum else None
+        _chk(lib().agx_ocp_clearance(self._h, C.c_int(n), _p(fr[0]), _p(fr[1]), _p(q), C.c_int(m), _p(dist), _p(wit), _p(dmin), _p(where)))
+        out = (dist,) + ((wit,) if witness else ()) + (((dmin, where),) if minimum else ())
+        return out[0] if len(out) == 1 else out
 
     # -- kernel level -------------------------------------------------------
     def calc_diff(self, want_tiles=True):

@@ -29,6 +29,10 @@ extern "C" int agx_cost_pairs_fill_ring_launch(void *stream, const DevCostWide *
 extern "C" int agx_diag_iter_log_launch(void *stream, const DevState *st, int B, int it, int phase, agx_iter_record *rec, int *n, int capacity);
 extern "C" int agx_diag_item_costs_launch(void *stream, int nv, int chain, const DevModel *m, const DevRows *rows2, int B, int T, const double *xs,
                                           const double *us, const RefView *rv, int R, double *cost, double *Lx, double *Lu, const void *obs);
+extern "C" int agx_diag_clearance_chunks(int m_samples);
+extern "C" int agx_diag_clearance_launch(void *stream, const DevModel *mp, int nv, int B, int n_pairs, const int *fa, const int *fb, const double *q,
+                                         long long qb, int qs, int m_samples, double *dist, double *witness, double *cmin, int *cidx,
+                                         double *min_dist, int *min_where, const void *obs);
 
 // launchers of the general-cost-row kernels of large models, likewise (agx_general_rows.hip; dest: the constants below)
 extern "C" int agx_general_rows_launch(int dest, void *stream, int nv, int prismatic, long long units, const DevModel *m, const DevOcp *o,
@@ -2137,6 +2141,64 @@ int agx_ocp_item_costs(agx_ocp *o, double *cost_r, double *Lx_r, double *Lu_r, d
           for (int i = 0; i < nvu; ++i) Lu_r[w * nvu + i] = h_Lu[u * NU + i];
       }
     }
+  return 0;
+}
+
+// Distances (and witness points, and the minimum) of the caller's pair list at the caller's configurations or at the iterate.
+// Reads only, as agx_ocp_item_costs: everything it writes on the device lies in d_clear, a block of its own.
+int agx_ocp_clearance(agx_ocp *o, int n_pairs, const int32_t *frame_a, const int32_t *frame_b, const double *q, int m, double *dist,
+                      double *witness, double *min_dist, int32_t *min_where) {
+  if (!o) return fail("agx_ocp_clearance: null handle");
+  if (!frame_a || !frame_b) return fail("agx_ocp_clearance: null pair arrays");
+  if (!dist) return fail("agx_ocp_clearance: null dist");
+  if (n_pairs < 1) return fail("agx_ocp_clearance: n_pairs must be at least 1");
+  if (m < 1) return fail("agx_ocp_clearance: m must be at least 1");
+  if (!q && m != o->T + 1) return fail("agx_ocp_clearance: q == NULL evaluates the iterate, m must be T + 1 = " + std::to_string(o->T + 1));
+  if ((long long)m * n_pairs > (long long)INT32_MAX) return fail("agx_ocp_clearance: m x n_pairs exceeds 2^31 - 1");
+  for (int p = 0; p < n_pairs; ++p) {
+    const std::string where = "agx_ocp_clearance: pair " + std::to_string(p) + ": ";
+    for (const int f : {(int)frame_a[p], (int)frame_b[p]}) {
+      if (f < 0 || f >= o->hm.nframes) return fail(where + "frame " + std::to_string(f) + " out of range");
+      if (!agx::frame_has_geometry(o->hm, f)) return fail(where + "frame " + std::to_string(f) + " carries no collision geometry");
+    }
+    if (agx::frame_is_box(o->hm, frame_a[p]) && agx::frame_is_box(o->hm, frame_b[p])) return fail(where + "box / box collision pairs are not supported");
+  }
+  if (set_device(o)) return -1;
+  const size_t B = o->B, NV = o->nv, items = B * m * n_pairs;
+  const int chunks = agx_diag_clearance_chunks(m);
+  // d_clear: dist | witness | chunk minima | min_dist | q (padded to the capacity) | then the ints: pairs a | pairs b | chunk items | min_where
+  const size_t n_wit = witness ? items * 9 : 0, n_q = q ? B * m * NV : 0;
+  const size_t n_dbl = items + n_wit + B * chunks + B + n_q, n_int = 2 * (size_t)n_pairs + B * chunks + 2 * B;
+  const size_t bytes = sizeof(double) * n_dbl + sizeof(int) * n_int;
+  if (bytes > o->clear_bytes) {  // (nothing queued uses the old block: every call ends with a wait for the stream)
+    HIPCHK(o->own.device_bytes(&o->d_clear, bytes));
+    o->clear_bytes = bytes;
+  }
+  double *d_dist = (double *)o->d_clear, *d_wit = d_dist + items, *d_cmin = d_wit + n_wit, *d_min = d_cmin + B * chunks, *d_q = d_min + B;
+  int *d_fa = (int *)(d_q + n_q), *d_fb = d_fa + n_pairs, *d_cidx = d_fb + n_pairs, *d_where = d_cidx + B * chunks;
+  std::vector<int> h_pairs(2 * (size_t)n_pairs);
+  for (int p = 0; p < n_pairs; ++p) { h_pairs[p] = frame_a[p]; h_pairs[n_pairs + p] = frame_b[p]; }
+  HIPCHK(hipMemcpyAsync(d_fa, h_pairs.data(), sizeof(int) * h_pairs.size(), hipMemcpyHostToDevice, o->stream));
+  std::vector<double> h_q;  // (alive until the wait below)
+  if (q) {
+    const double *src = q;
+    if (o->padded) {
+      h_q.assign(n_q, 0.0);
+      pad_rows(h_q.data(), q, B * m, 1, o->nvu, o->nv, 0.0);
+      src = h_q.data();
+    }
+    HIPCHK(hipMemcpyAsync(d_q, src, sizeof(double) * n_q, hipMemcpyHostToDevice, o->stream));
+  }
+  const bool want_min = min_dist || min_where;
+  HIPCHK((hipError_t)agx_diag_clearance_launch((void *)o->stream, o->d_model, o->nv, o->B, n_pairs, d_fa, d_fb, q ? d_q : o->d_xs,
+                                               q ? (long long)m * o->nv : (long long)(o->T + 1) * o->nx, q ? o->nv : o->nx, m, d_dist,
+                                               witness ? d_wit : nullptr, d_cmin, d_cidx, want_min ? d_min : nullptr, d_where,
+                                               o->obs_set ? o->d_obs : nullptr));
+  HIPCHK(hipMemcpyAsync(dist, d_dist, sizeof(double) * items, hipMemcpyDeviceToHost, o->stream));
+  if (witness) HIPCHK(hipMemcpyAsync(witness, d_wit, sizeof(double) * n_wit, hipMemcpyDeviceToHost, o->stream));
+  if (min_dist) HIPCHK(hipMemcpyAsync(min_dist, d_min, sizeof(double) * B, hipMemcpyDeviceToHost, o->stream));
+  if (min_where) HIPCHK(hipMemcpyAsync(min_where, d_where, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, o->stream));
+  HIPCHK(hipStreamSynchronize(o->stream));
   return 0;
 }
 

@@ -268,6 +268,9 @@ struct agx_ocp {
   // staging of agx_ocp_item_costs (cost | Lx | Lu of every node and row at the capacity), grown on demand
   double *d_items = nullptr;
   size_t items_bytes = 0;
+  // block of agx_ocp_clearance (the call's pair table, its padded configurations and its results), grown on demand
+  void *d_clear = nullptr;
+  size_t clear_bytes = 0;
   // in-situ kernel timing (agx_ocp_profile): event pairs around the launches of the SQP loop
   bool prof = false;
   std::deque<hipEvent_t> prof_ev;  // [2 * k] start, [2 * k + 1] stop (a deque, as st_tev); the first prof_used are recorded in the running solve

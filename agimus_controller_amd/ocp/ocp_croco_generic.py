@@ -814,6 +814,26 @@ class OCPCrocoGeneric(OCPBaseCroco):
         self._hip.upload_warmstart(xs, us)
         return assemble_cost_items([i.name for i in self._items(False)], [i.name for i in self._items(True)], self._hip.item_costs())
 
+    def clearance(self, states=None, witness: bool = False):
+        """Signed distance of EVERY collision pair of `robot_models.collision_model` -- not only the pairs the YAML turns into
+        cost items or constraints -- at every node of the last solve's prediction (states None: the handle's resident iterate) or
+        at the given states [m][nx] (or configurations [m][nv]).  Returns (names, dist) with names "a|b" and dist [m][n_pairs], and
+        with witness=True also [m][n_pairs][3][3]: point on a, point on b, unit normal (HipOcp.clearance).  Reads only: unlike
+        `cost_items`, the given states do not become the iterate."""
+        cmodel = self._collision_model
+        if cmodel is None or not cmodel.collisionPairs:
+            raise RuntimeError("the collision model has no collision pair")
+        fn = self._table.frame_names
+        names = [f"{fn[a]}|{fn[b]}" for a, b in cmodel.collisionPairs]
+        q = None
+        if states is not None:
+            q = np.asarray(states, dtype=np.float64)
+            if q.ndim != 2 or q.shape[0] < 1 or q.shape[1] not in (self._nv, self._nx):
+                raise ValueError(f"states: expected shape (m, {self._nx}) or (m, {self._nv}), got {q.shape}")
+            q = q[None, :, : self._nv]
+        out = self._hip.clearance(cmodel.collisionPairs, q, witness=witness)
+        return (names, out[0][0], out[1][0]) if witness else (names, out[0])
+
     @staticmethod
     def get_default_yaml_file(basename: str) -> pathlib.Path:
         return pathlib.Path(__file__).parent / basename

@@ -384,6 +384,30 @@ int agx_ocp_iter_log_read(agx_ocp *ocp, agx_iter_record *out, int32_t *n);
  * node types) in a device buffer the handle keeps (grown on demand, never shrunk) and in a host buffer of the same size for the
  * duration of the call -- several hundred MB at a batch of 1024 with a wide cost set; probe a few instances' worth of batch.   */
 int agx_ocp_item_costs(agx_ocp *ocp, double *cost_r, double *Lx_r, double *Lu_r, double *cost_t, double *Lx_t);
+/* Clearance report: how far apart the geometries of a pair list are, at configurations of the caller's choice.
+ *   frame_a[p], frame_b[p]  geometry frames of the handle's model, n_pairs >= 1 of them and no upper limit: any pairs, rows of the
+ *                           problem or not, self pairs, a pair listed twice.  The table is uploaded with every call.
+ *   q [B][m][nv]            the caller's joints (before padding, as agx_model_frame_placement takes them), m >= 1 samples per
+ *                           instance; NULL: the handle's current iterate, m must be T + 1 and sample t is node t of xs, the
+ *                           terminal node included.
+ *   dist [B][m][n_pairs]    the signed distance, the function the collision cost rows and constraints evaluate
+ *                           (collision_distance_placed: capsule, sphere and box; negative in penetration).
+ *   witness [B][m][n_pairs][9]  optional: the point on geometry a, the point on geometry b and the unit normal n, world frame.
+ *                           The points lie on the SURFACES (the device routine's points on a capsule's axis or at a sphere's
+ *                           centre, moved by the radius along n), so pa - pb = dist n.  Coincident axis points leave n = 0.
+ *   min_dist [B]            optional: the smallest distance of instance b over samples and pairs;
+ *   min_where [B][2]        optional: its sample and pair; of equal distances the lowest sample, then the lowest pair.  A fixed-order
+ *                           reduction without atomics: the same bits from run to run.  (-1, -1) and +inf where no distance is finite.
+ * World-fixed frames are placed as the solve places them: by the latest agx_ocp_set_geom_placement and, for a listed frame on
+ * the 7-joint capacity, by instance b's entry of agx_ocp_set_obstacle_placements.
+ * The call only reads: it runs on the handle's stream in a device block of its own, waits for the stream and leaves the iterate,
+ * the multipliers, the tiles and their carry, the first-node record and the resident trajectory as they are; a solve or MPC step
+ * after it gives the bits it would have given without it.  Kernels: k_clearance (a workgroup per eight samples of an instance,
+ * every model capacity), k_clearance_min.
+ * Refused, naming the pair where there is one: null handle, pair arrays or dist; n_pairs < 1; m < 1; q == NULL with
+ * m != T + 1; a frame out of range or without collision geometry; a box / box pair.                                        */
+int agx_ocp_clearance(agx_ocp *ocp, int n_pairs, const int32_t *frame_a, const int32_t *frame_b, const double *q, int m, double *dist,
+                      double *witness, double *min_dist, int32_t *min_where);
 
 /* ---- kernel-level entry points (parity tests and bench instrumentation) - */
 /* Node-parallel derivative pass at the resident (xs, us): writes the tiles to

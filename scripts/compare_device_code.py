@@ -8,9 +8,9 @@ rename flags of backend.build(), agx_cost_pairs.hip, agx_diag.hip) both trees ar
 flags of the build.  The assembly is cut into functions keyed by their mangled name (moving host code changes the order in which
 template instantiations are emitted) and compared as plain text after two artefacts of the compile are normalised: the
 `__hip_cuid_<hash>` symbol, which depends on the directory a source is compiled from, and the function index in local labels
-(`.LBB<n>_<k>` and the `BB<n>_<k>` of the loop comments, `.Lfunc_end<n>`, `.LJTI<n>_<k>`).  The
-`-Rpass-analysis=kernel-resource-usage` remarks of the same compiles are compared per kernel too (registers, scratch, LDS,
-occupancy).  Prints the count of kernels per unit and every name that differs; exit status 1 if anything does."""
+(`.LBB<n>_<k>` and the `BB<n>_<k>` of the loop comments, `.Lfunc_end<n>`, `.LJTI<n>_<k>`, and the padding in front of a
+label's comment, which follows the width of that index).  The `-Rpass-analysis=kernel-resource-usage` remarks of the same
+compiles are compared per kernel too (registers, scratch, LDS, occupancy).  Prints the count of kernels per unit and every name that differs; exit status 1 if anything does."""
 from __future__ import annotations
 
 import argparse
@@ -51,7 +51,8 @@ def compile_unit(tree: str, unit: str, out: str):
 
 
 _NORMALISE = ((re.compile(r"__hip_cuid_[0-9a-f]+"), "__hip_cuid_"), (re.compile(r"(\.L|\b)BB\d+_"), r"\1BB_"),
-              (re.compile(r"\.Lfunc_(begin|end)\d+"), r".Lfunc_\1"), (re.compile(r"\.LJTI\d+_"), ".LJTI_"))
+              (re.compile(r"\.Lfunc_(begin|end)\d+"), r".Lfunc_\1"), (re.compile(r"\.LJTI\d+_"), ".LJTI_"),
+              (re.compile(r"^(\.LBB_\d+:)\s+;"), r"\1 ;"))  # (the comment column moves when the function index gains a digit)
 
 
 def functions(asm: str):
