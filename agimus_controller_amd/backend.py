@@ -503,14 +503,18 @@ class HipOcp:
         qt = np.empty((self.B, self.T + 1, qs.value))
         aux = np.empty((self.B, self.T + 1, as_.value))
         _chk(lib().agx_ocp_qp_tiles(self._h, _p(qt), _p(aux), C.byref(qs), C.byref(as_)))
-        nv, ld = self.nv, (8 if self.nv <= 8 else 32)
-        b2 = nv * ld
-        blk = lambda a, off: a[..., off:off + b2].reshape(self.B, self.T + 1, nv, ld)[..., :nv]  # noqa: E731
+        # the tiles are laid out at the handle's capacity NV >= nv (a model below a capacity is padded with joints at the end)
+        nv, ld = self.nv, (8 if (qs.value - 48) % 48 == 0 and (qs.value - 48) // 48 <= 8 else 32)
+        NV = (qs.value - 5 * ld - 8) // (6 * ld)
+        assert NV >= nv and qs.value == 6 * NV * ld + 5 * ld + 8 and as_.value == 4 * NV * ld + 3 * ld, (nv, qs.value, as_.value)
+        b2 = NV * ld
+        blk = lambda a, off: a[..., off:off + b2].reshape(self.B, self.T + 1, NV, ld)[..., :nv, :nv]  # noqa: E731
+        pair = lambda a, off: np.concatenate([a[..., off:off + nv], a[..., off + NV:off + NV + nv]], axis=-1)  # noqa: E731
         q = {name: blk(qt, k * b2) for k, name in enumerate(("Hqq", "Hqv", "Hvv", "Hqw", "Hvw", "Hww"))}
         o = 6 * b2
-        q["gx"] = qt[..., o:o + 2 * nv]
+        q["gx"] = pair(qt, o)
         q["gw"] = qt[..., o + 2 * ld:o + 2 * ld + nv]
-        q["f"] = qt[..., o + 3 * ld:o + 3 * ld + 2 * nv]
+        q["f"] = pair(qt, o + 3 * ld)
         q["cost"] = qt[..., o + 5 * ld]
         a = {name: blk(aux, k * b2) for k, name in enumerate(("M", "tq", "tv", "Lqq"))}
         o = 4 * b2

@@ -726,12 +726,18 @@ AGX_UNROLL_NV
 // pinocchio::log3 including its explicit branch near pi (spatial/log.hxx); the
 // branch decides the sign of the axis at theta = pi, which the reference's golden
 // solution depends on (Panda tool frame at q = 0 is exactly pi from identity).
+// Inside that branch theta is pi - asin(|vee(R - R')| / 2), the asin by its series (the argument is below 1e-2: the term left
+// out is below 1e-20): acos of the trace turns the rounding of R into eps / (pi - theta) there.  On a rotation the two agree;
+// pi exactly gives the same bits.
 AGX_DEV void log3(const double *R, double *w) {
   double tr = R[0] + R[4] + R[8];
   tr = fmin(3.0, fmax(-1.0, tr));
   const double ct = 0.5 * (tr - 1.0);
-  const double theta = acos(ct);
+  double theta = acos(ct);
   if (theta >= 3.14159265358979323846 - 1e-2) {
+    const double a0 = R[7] - R[5], a1 = R[2] - R[6], a2 = R[3] - R[1];
+    const double sn2 = 0.25 * (a0 * a0 + a1 * a1 + a2 * a2);
+    theta = 3.14159265358979323846 - sqrt(sn2) * (1.0 + sn2 * (1.0 / 6.0 + sn2 * (3.0 / 40.0 + sn2 * (15.0 / 336.0))));
     const double cphi = -ct;
     const double beta = theta * theta / (1.0 + cphi);
     const double v0 = (R[0] + cphi) * beta, v1 = (R[4] + cphi) * beta, v2 = (R[8] + cphi) * beta;
@@ -745,19 +751,33 @@ AGX_DEV void log3(const double *R, double *w) {
     w[2] = t * (R[3] - R[1]);
   }
 }
-AGX_DEV void jlog3(const double *w, double *J) {
-  const double t2 = dot3(w, w), t = sqrt(t2);
-  double alpha, diag;
-  if (t < 1e-4) {
-    alpha = 1.0 / 12.0 + t2 / 720.0;
-    diag = 0.5 * (2.0 - t2 / 6.0);
+// The three scalar functions of t = |w| that log6, Jlog3 and Jlog6 are made of:
+//   A = (t/2) cot(t/2)   (alpha of log6, the diagonal term of Jlog3)
+//   beta = (1 - A) / t^2 (beta of log6 and Jlog6, alpha of Jlog3)        bdot = beta'(t) / t   (Jlog6)
+// pinocchio forms them with 1 - cos t and switches to two Taylor terms below t = 1e-6 (log6) or 1e-4 (Jlog3, Jlog6), which
+// leaves 4 to 8 digits for t in [1e-6, 1e-3].  Here: below t = 1/2 the series beta = sum_n |B_2n| / (2n)! t^(2n-2) (radius 2 pi,
+// seven terms: the first one left out is below 3e-16 of beta and 3e-15 of bdot) and A = 1 - t^2 beta; from t = 1/2 on the half
+// angle, where (1 - A) / t^2 loses under two digits and the three terms of bdot three, of a quantity that enters the result times
+// t^2 |p|: under 1e-14 in both.  (Ten terms and the switch at t = 1 cost the eight-lane derivative kernel 36 bytes of scratch.)
+AGX_DEV void log_coeffs(double t2, double &A, double &beta, double &bdot) {
+  if (t2 < 0.25) {
+    beta = 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0 + t2 * (1.0 / 47900160.0 + t2 * (
+           5.284190138687493e-10 + t2 * 1.3382536530684679e-11)))));
+    bdot = 2.0 / 720.0 + t2 * (4.0 / 30240.0 + t2 * (6.0 / 1209600.0 + t2 * (8.0 / 47900160.0 + t2 * (10.0 * 5.284190138687493e-10 +
+           t2 * (12.0 * 1.3382536530684679e-11 + t2 * (14.0 * 3.3896802963225827e-13))))));
+    A = 1.0 - t2 * beta;
   } else {
-    double st, ct;
-    sincos(t, &st, &ct);
-    const double s1 = st / (1.0 - ct);
-    alpha = 1.0 / t2 - s1 / (2.0 * t);
-    diag = 0.5 * t * s1;
+    const double t = sqrt(t2), t2inv = 1.0 / t2;
+    double sh, ch;
+    sincos(0.5 * t, &sh, &ch);
+    A = 0.5 * t * ch / sh;
+    beta = (1.0 - A) * t2inv;
+    bdot = (0.25 / (sh * sh) - t2inv - beta) * t2inv;
   }
+}
+AGX_DEV void jlog3(const double *w, double *J) {
+  double diag, alpha, bdot;
+  log_coeffs(dot3(w, w), diag, alpha, bdot);
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -772,22 +792,8 @@ AGX_DEV void log6(const double *R, const double *p, double *r, double *TL, doubl
   double w[3];
   log3(R, w);
   const double t2 = dot3(w, w);
-  double alpha, beta, bdot = 1.0 / 360.0;
-  const double t = sqrt(t2);
-  if (t2 < 1e-12) {
-    alpha = 1.0 - t2 / 12.0;
-    beta = 1.0 / 12.0 + t2 / 720.0;
-  } else {
-    double st, ct;
-    sincos(t, &st, &ct);
-    const double i22 = 1.0 / (2.0 * (1.0 - ct));
-    alpha = t * st * i22;
-    beta = 1.0 / t2 - st / t * i22;
-    if (t >= 1e-4) {
-      const double tinv = 1.0 / t, t2inv = tinv * tinv;
-      bdot = -2.0 * t2inv * t2inv + (1.0 + st * tinv) * t2inv * i22;
-    }
-  }
+  double alpha, beta, bdot;
+  log_coeffs(t2, alpha, beta, bdot);
   double wxp[3];
   cross3(w, p, wxp);
   const double wp = dot3(w, p);
@@ -797,17 +803,21 @@ AGX_DEV void log6(const double *R, const double *p, double *r, double *TL, doubl
     r[3 + e] = w[e];
   }
   if (JAC) {
-    jlog3(w, TL);
-    // pinocchio::Jlog6 uses the Taylor beta below 1e-4 (not 1e-6): keep its thresholds
-    double betaJ = beta;
-    if (t < 1e-4) betaJ = 1.0 / 12.0 + t2 / 720.0;
-    double v3[3], C[9];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) v3[e] = (bdot * wp) * w[e] - (t2 * bdot + 2.0 * betaJ) * p[e];
+    // TL = Jlog3(w) from the same three coefficients
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-      for (int j = 0; j < 3; ++j) C[3 * i + j] = v3[i] * w[j] + betaJ * w[i] * p[j] + (i == j ? wp * betaJ : 0.0);
+      for (int j = 0; j < 3; ++j) TL[3 * i + j] = beta * w[i] * w[j] + (i == j ? alpha : 0.0);
+    TL[1] -= 0.5 * w[2]; TL[2] += 0.5 * w[1];
+    TL[3] += 0.5 * w[2]; TL[5] -= 0.5 * w[0];
+    TL[6] -= 0.5 * w[1]; TL[7] += 0.5 * w[0];
+    double v3[3], C[9];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) v3[e] = (bdot * wp) * w[e] - (t2 * bdot + 2.0 * beta) * p[e];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) C[3 * i + j] = v3[i] * w[j] + beta * w[i] * p[j] + (i == j ? wp * beta : 0.0);
     C[1] -= 0.5 * p[2]; C[2] += 0.5 * p[1];
     C[3] += 0.5 * p[2]; C[5] -= 0.5 * p[0];
     C[6] -= 0.5 * p[1]; C[7] += 0.5 * p[0];
@@ -958,10 +968,27 @@ AGX_DEV void closest_seg_seg(const double *a0, const double *a1, const double *b
   if (e <= eps) { t = 0.0; s = clamp01(-c / a); return; }
   const double b = dot3(d1, d2);
   const double denom = a * e - b * b;
-  s = (denom > eps * a * e) ? clamp01((b * f - c * e) / denom) : 0.0;
-  t = (b * s + f) / e;
-  if (t < 0.0) { t = 0.0; s = clamp01(-c / a); }
-  else if (t > 1.0) { t = 1.0; s = clamp01((b - c) / a); }
+  // t of the point of B closest to A(s0), clamped, and s moved along with a clamped t
+  auto from_s = [&](double s0, double &so, double &to) {
+    so = s0;
+    to = (b * s0 + f) / e;
+    if (to < 0.0) { to = 0.0; so = clamp01(-c / a); }
+    else if (to > 1.0) { to = 1.0; so = clamp01((b - c) / a); }
+  };
+  if (denom > eps * a * e) { from_s(clamp01((b * f - c * e) / denom), s, t); return; }
+  // (nearly) parallel, tilt below 1e-7 rad: along the overlap the distance is linear up to the tilt squared, so the closest
+  // points sit at an end of A or of B.  Start from both ends of A and keep the closer pair (starting from s = 0 alone is off by
+  // tilt x length when the segments converge towards the other end).
+  double s1, t1, g0 = 0.0, g1 = 0.0;
+  from_s(0.0, s, t);
+  from_s(1.0, s1, t1);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double u0 = r[k] + s * d1[k] - t * d2[k], u1 = r[k] + s1 * d1[k] - t1 * d2[k];
+    g0 += u0 * u0;
+    g1 += u1 * u1;
+  }
+  if (g1 < g0) { s = s1; t = t1; }
 }
 
 // Parameter s in [-h, h] of the point of the segment c + s d closest to the box |x_i| <= b_i (all in

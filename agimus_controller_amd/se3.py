@@ -120,32 +120,46 @@ class Force(_Spatial6):
 
 
 def log3(R) -> np.ndarray:
-    """pinocchio.log3 (axis-angle vector of a rotation), with its branch near theta = pi."""
+    """pinocchio.log3 (axis-angle vector of a rotation), with its branch near theta = pi; inside that branch theta is
+    pi - asin(|vee(R - R')| / 2) by the series of asin, as csrc/agx_device.hpp log3 has it."""
     R = np.asarray(R, dtype=float).reshape(3, 3)
     ct = 0.5 * (min(3.0, max(-1.0, float(np.trace(R)))) - 1.0)
     theta = np.arccos(ct)
+    a = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
     if theta >= np.pi - 1e-2:
+        sn2 = 0.25 * float(a @ a)
+        theta = np.pi - np.sqrt(sn2) * (1.0 + sn2 * (1.0 / 6.0 + sn2 * (3.0 / 40.0 + sn2 * (15.0 / 336.0))))
         cphi = -ct
         beta = theta * theta / (1.0 + cphi)
         v = (np.diag(R) + cphi) * beta
         sgn = np.array([1.0 if R[2, 1] > R[1, 2] else -1.0, 1.0 if R[0, 2] > R[2, 0] else -1.0, 1.0 if R[1, 0] > R[0, 1] else -1.0])
         return sgn * np.sqrt(np.maximum(v, 0.0))
     t = 0.5 * (theta / np.sin(theta) if theta > 1e-8 else 1.0)
-    return t * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    return t * a
+
+
+_LOG_SERIES = (1.0 / 12.0, 1.0 / 720.0, 1.0 / 30240.0, 1.0 / 1209600.0, 1.0 / 47900160.0, 5.284190138687493e-10, 1.3382536530684679e-11)
+
+
+def log_coeffs(t2):
+    """(A, beta) of log6 at t2 = |w|^2 (scalar or array): A = (t/2) cot(t/2), beta = (1 - A) / t^2, by the series in t^2 below
+    t = 1/2 and the half angle above -- csrc/agx_device.hpp log_coeffs; no 1 - cos t, which leaves 4 to 8 digits for small t."""
+    t2 = np.asarray(t2, dtype=float)
+    series = 0.0
+    for c in reversed(_LOG_SERIES):
+        series = c + t2 * series
+    big = t2 >= 0.25
+    t2b = np.where(big, t2, 1.0)
+    h = 0.5 * np.sqrt(t2b)
+    Ab = h * np.cos(h) / np.sin(h)
+    return np.where(big, Ab, 1.0 - t2 * series), np.where(big, (1.0 - Ab) / t2b, series)
 
 
 def log6(M: "SE3") -> "Motion":
     """pinocchio.log6: Motion (linear, angular) with exp6(log6(M)) = M."""
     w = log3(M.rotation)
     p = np.asarray(M.translation, dtype=float)
-    t2 = float(w @ w)
-    t = np.sqrt(t2)
-    if t2 < 1e-12:
-        alpha, beta = 1.0 - t2 / 12.0, 1.0 / 12.0 + t2 / 720.0
-    else:
-        st, ct = np.sin(t), np.cos(t)
-        i22 = 1.0 / (2.0 * (1.0 - ct))
-        alpha, beta = t * st * i22, 1.0 / t2 - st / t * i22
+    alpha, beta = (float(x) for x in log_coeffs(float(w @ w)))
     v = alpha * p - 0.5 * np.cross(w, p) + beta * float(w @ p) * w
     return Motion(np.concatenate([v, w]))
 

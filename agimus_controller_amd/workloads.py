@@ -241,7 +241,7 @@ def generic_batch_arrays(B: int, n_points: int, dt: float, nv: int = 7, seed0: i
 def _log6_batch(R, p):
     """pinocchio.log6 of n placements (R [n,3,3], p [n,3]) -> [n,6] (linear | angular); the branch near
     theta = pi of log3 is not needed for inverse-kinematics errors and falls back to the scalar code."""
-    from .se3 import SE3, log6
+    from .se3 import SE3, log6, log_coeffs
 
     n = R.shape[0]
     ct = 0.5 * (np.clip(np.trace(R, axis1=1, axis2=2), -1.0, 3.0) - 1.0)
@@ -251,14 +251,7 @@ def _log6_batch(R, p):
     small = theta <= 1e-8
     tt = 0.5 * np.where(small, 1.0, theta / np.where(small, 1.0, np.sin(theta)))
     w = tt[:, None] * np.stack([R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]], axis=1)
-    t2 = np.einsum("ni,ni->n", w, w)
-    t = np.sqrt(t2)
-    tiny = t2 < 1e-12
-    t2s, ts = np.where(tiny, 1.0, t2), np.where(tiny, 1.0, t)
-    st, ctt = np.sin(ts), np.cos(ts)
-    i22 = 1.0 / np.where(tiny, 1.0, 2.0 * (1.0 - ctt))
-    alpha = np.where(tiny, 1.0 - t2 / 12.0, ts * st * i22)
-    beta = np.where(tiny, 1.0 / 12.0 + t2 / 720.0, 1.0 / t2s - st / ts * i22)
+    alpha, beta = log_coeffs(np.einsum("ni,ni->n", w, w))
     v = alpha[:, None] * p - 0.5 * np.cross(w, p) + (beta * np.einsum("ni,ni->n", w, p))[:, None] * w
     return np.concatenate([v, w], axis=1)
 

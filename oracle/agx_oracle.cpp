@@ -364,8 +364,12 @@ inline void log3d(const double *R, double *w) {
   if (tr > 3.0) tr = 3.0;
   if (tr < -1.0) tr = -1.0;
   const double ct = 0.5 * (tr - 1.0);
-  const double theta = std::acos(ct);
+  double theta = std::acos(ct);
   if (theta >= M_PI - 1e-2) {
+    // theta = pi - asin(|vee(R - R')| / 2) by the series of asin, not acos of the trace (eps / (pi - theta)); see agx_device.hpp
+    const double a0 = R[7] - R[5], a1 = R[2] - R[6], a2 = R[3] - R[1];
+    const double sn2 = 0.25 * (a0 * a0 + a1 * a1 + a2 * a2);
+    theta = M_PI - std::sqrt(sn2) * (1.0 + sn2 * (1.0 / 6.0 + sn2 * (3.0 / 40.0 + sn2 * (15.0 / 336.0))));
     const double cphi = -ct;
     const double beta = theta * theta / (1.0 + cphi);
     const double v0 = (R[0] + cphi) * beta, v1 = (R[4] + cphi) * beta, v2 = (R[8] + cphi) * beta;
@@ -379,19 +383,31 @@ inline void log3d(const double *R, double *w) {
     w[2] = t * (R[3] - R[1]);
   }
 }
+// A = (t/2) cot(t/2), beta = (1 - A) / t^2, bdot = beta'(t) / t: the scalar functions of log6, Jlog3 and Jlog6.  Series in
+// t^2 below t = 1/2 (coefficients |B_2n| / (2n)!, seven terms), half angle above: no 1 - cos t anywhere (agx_device.hpp log_coeffs).
+inline void log_coeffs(double t2, double &A, double &beta, double &bdot) {
+  if (t2 < 0.25) {
+    static const double c[11] = {1.0 / 12.0, 1.0 / 720.0, 1.0 / 30240.0, 1.0 / 1209600.0, 1.0 / 47900160.0, 5.284190138687493e-10,
+                                 1.3382536530684679e-11, 3.3896802963225827e-13, 8.586062056277845e-15, 2.174868698558062e-16,
+                                 5.5090028283602295e-18};
+    beta = 0.0;
+    for (int n = 6; n >= 0; --n) beta = c[n] + t2 * beta;
+    bdot = 0.0;
+    for (int n = 7; n >= 1; --n) bdot = 2.0 * n * c[n] + t2 * bdot;
+    A = 1.0 - t2 * beta;
+  } else {
+    const double t = std::sqrt(t2), sh = std::sin(0.5 * t), ch = std::cos(0.5 * t);
+    A = 0.5 * t * ch / sh;
+    beta = (1.0 - A) / t2;
+    bdot = (0.25 / (sh * sh) - 1.0 / t2 - beta) / t2;
+  }
+}
 inline void log6d(const double *R, const double *p, double *r) {
   double w[3];
   log3d(R, w);
   const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  double alpha, beta;
-  if (t2 < 1e-12) {
-    alpha = 1.0 - t2 / 12.0;
-    beta = 1.0 / 12.0 + t2 / 720.0;
-  } else {
-    const double t = std::sqrt(t2), st = std::sin(t), ct = std::cos(t);
-    alpha = t * st / (2.0 * (1.0 - ct));
-    beta = 1.0 / t2 - st / (2.0 * t * (1.0 - ct));
-  }
+  double alpha, beta, bdot;
+  log_coeffs(t2, alpha, beta, bdot);
   double wxp[3];
   cross(w, p, wxp);
   const double wp = w[0] * p[0] + w[1] * p[1] + w[2] * p[2];
@@ -402,16 +418,8 @@ inline void log6d(const double *R, const double *p, double *r) {
 }
 // Jlog3 / Jlog6 for a right (local) perturbation, pinocchio::Jlog3 / Jlog6.
 inline void jlog3d(const double *w, double *J) {
-  const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], t = std::sqrt(t2);
-  double alpha, diag;
-  if (t < 1e-4) {
-    alpha = 1.0 / 12.0 + t2 / 720.0;
-    diag = 0.5 * (2.0 - t2 / 6.0);
-  } else {
-    const double st = std::sin(t), ct = std::cos(t), s1 = st / (1.0 - ct);
-    alpha = 1.0 / t2 - s1 / (2.0 * t);
-    diag = 0.5 * t * s1;
-  }
+  double alpha, diag, bdot;
+  log_coeffs(w[0] * w[0] + w[1] * w[1] + w[2] * w[2], diag, alpha, bdot);
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) J[3 * i + j] = alpha * w[i] * w[j] + (i == j ? diag : 0.0);
   J[1] -= 0.5 * w[2]; J[2] += 0.5 * w[1];
@@ -422,16 +430,9 @@ inline void jlog6d(const double *R, const double *p, double *J /*6x6*/) {
   double w[3], TL[9];
   log3d(R, w);
   jlog3d(w, TL);
-  const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], t = std::sqrt(t2);
-  double beta, bdot;
-  if (t < 1e-4) {
-    beta = 1.0 / 12.0 + t2 / 720.0;
-    bdot = 1.0 / 360.0;
-  } else {
-    const double tinv = 1.0 / t, t2inv = tinv * tinv, st = std::sin(t), ct = std::cos(t), i22 = 1.0 / (2.0 * (1.0 - ct));
-    beta = t2inv - st * tinv * i22;
-    bdot = -2.0 * t2inv * t2inv + (1.0 + st * tinv) * t2inv * i22;
-  }
+  const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  double A, beta, bdot;
+  log_coeffs(t2, A, beta, bdot);
   const double wp = w[0] * p[0] + w[1] * p[1] + w[2] * p[2];
   double v3[3], Cm[9], TR[9];
   for (int k = 0; k < 3; ++k) v3[k] = (bdot * wp) * w[k] - (t2 * bdot + 2.0 * beta) * p[k];
@@ -550,10 +551,26 @@ void closest_seg_seg(const double *a0, const double *a1, const double *b0, const
   if (e <= eps) { t = 0.0; s = clamp01(-c / a); return; }
   const double b = d1[0] * d2[0] + d1[1] * d2[1] + d1[2] * d2[2];
   const double denom = a * e - b * b;
-  s = (denom > eps * a * e) ? clamp01((b * f - c * e) / denom) : 0.0;
-  t = (b * s + f) / e;
-  if (t < 0.0) { t = 0.0; s = clamp01(-c / a); }
-  else if (t > 1.0) { t = 1.0; s = clamp01((b - c) / a); }
+  // t of the point of B closest to A(s0), clamped, and s moved along with a clamped t
+  auto from_s = [&](double s0, double &so, double &to) {
+    so = s0;
+    to = (b * s0 + f) / e;
+    if (to < 0.0) { to = 0.0; so = clamp01(-c / a); }
+    else if (to > 1.0) { to = 1.0; so = clamp01((b - c) / a); }
+  };
+  if (denom > eps * a * e) { from_s(clamp01((b * f - c * e) / denom), s, t); return; }
+  // (nearly) parallel, tilt below 1e-7 rad: along the overlap the distance is linear up to the tilt squared, so the closest
+  // points sit at an end of A or of B.  Start from both ends of A and keep the closer pair (starting from s = 0 alone is off by
+  // tilt x length when the segments converge towards the other end).
+  double s1, t1, g0 = 0.0, g1 = 0.0;
+  from_s(0.0, s, t);
+  from_s(1.0, s1, t1);
+  for (int k = 0; k < 3; ++k) {
+    const double u0 = r[k] + s * d1[k] - t * d2[k], u1 = r[k] + s1 * d1[k] - t1 * d2[k];
+    g0 += u0 * u0;
+    g1 += u1 * u1;
+  }
+  if (g1 < g0) { s = s1; t = t1; }
 }
 
 // parameter s in [-h, h] of the point of the segment c + s d closest to the box |x_i| <= b_i (box

@@ -5,7 +5,10 @@ The reference is closed forms on top of the forward kinematics of tests/joint_re
 sphere / sphere, sphere / capsule and capsule / capsule as point / point, point / segment and segment / segment distances minus
 the radii, and the distance of a point to the SURFACE of a sphere, a capsule or a box for the witness points.  The segment /
 segment distance is written as the smallest of the interior stationary point and the four end-point-to-segment distances, not
-as the clamped sequence of the device routine.  Box pairs have no closed form here: their reference is the checker.
+as the clamped sequence of the device routine.  The box pairs of the 64-pair chain case have the checker as their reference.
+
+Box against capsule or sphere and the degenerate capsule pairs (parallel, nearly parallel, collinear, crossing axes) have an exact
+reference of their own further down, on world-fixed frames and in numpy longdouble: `degenerate_scene` and `exact_distance`.
 """
 import ctypes as C
 
@@ -125,6 +128,137 @@ def reference(t, pairs, q):
     return np.stack([distance(t, a, b, q) for a, b in ids], -1)
 
 
+# ------------------------------------------------------------------------------- exact references on world-fixed frames
+LD = np.longdouble
+
+
+def segment_box(e0, e1, half):
+    """Distance of the segment e0 e1 (box frame; e0 == e1: a point) to the box [-half, half], 0 when they meet.  Along the segment
+    dist^2 = sum_k max(|x_k| - half_k, 0)^2 is piecewise quadratic with breakpoints where a coordinate meets +- half_k: the
+    smallest of its values at the breakpoints, at the ends and at the clamped minimiser of every piece."""
+    e0, e1, half = (np.asarray(v, dtype=LD) for v in (e0, e1, half))
+    d = e1 - e0
+
+    def f2(s):
+        o = np.maximum(np.abs(e0 + s * d) - half, LD(0))
+        return (o * o).sum()
+
+    cuts = {LD(0), LD(1)}
+    for k in range(3):
+        for sg in (-1, 1):
+            if d[k] != 0 and 0 < (sg * half[k] - e0[k]) / d[k] < 1:
+                cuts.add((sg * half[k] - e0[k]) / d[k])
+    cuts = sorted(cuts)
+    best = min(f2(s) for s in cuts)
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        xm = e0 + (lo + hi) / 2 * d
+        act = np.abs(xm) > half
+        if not act.any():
+            return LD(0)
+        den = (d[act] ** 2).sum()
+        if den > 0:
+            s = -(d[act] * (e0[act] - np.sign(xm[act]) * half[act])).sum() / den
+            best = min(best, f2(min(max(s, lo), hi)))
+    return np.sqrt(best)
+
+
+def _world_ld(t, f):
+    assert t.frame_parent[f] < 0, "world-fixed frames only"
+    pl = np.asarray(t.frame_placement, dtype=LD).reshape(-1, 12)[f]
+    hl = LD(0) if t.frame_halflen is None else LD(t.frame_halflen[f])
+    box = np.asarray(t.frame_box, dtype=LD).reshape(-1, 3)[f] if is_box(t, f) else None
+    return pl[:9].reshape(3, 3), pl[9:], LD(t.frame_radius[f]), hl, box
+
+
+def exact_distance(t, fa, fb):
+    """Signed distance of a pair of world-fixed geometry frames from the stored doubles, in longdouble: sphere / capsule pairs by
+    the closed forms above, a box against a sphere or capsule by segment_box; a sphere centre inside the box gives minus the depth
+    to the nearest face, minus the radius (the definition of the overlap)."""
+    Ra, pa, ra, ha, ba = _world_ld(t, fa)
+    Rb, pb, rb, hb, bb = _world_ld(t, fb)
+    assert ba is None or bb is None, "box / box pairs are not supported"
+    if bb is None and ba is not None:
+        (Ra, pa, ra, ha, ba), (Rb, pb, rb, hb, bb) = (Rb, pb, rb, hb, bb), (Ra, pa, ra, ha, ba)
+    a0, a1 = _ends(Ra, pa, ha)
+    if bb is not None:
+        l0, l1 = Rb.T @ (a0 - pb), Rb.T @ (a1 - pb)
+        d = segment_box(l0, l1, bb)
+        if d == 0:
+            assert ha == 0, "a capsule axis that meets the box has no reference here"
+            return -(bb - np.abs(l0)).min() - ra
+        return d - ra
+    b0, b1 = _ends(Rb, pb, hb)
+    if ha == 0 and hb == 0:
+        d = np.sqrt(((pa - pb) ** 2).sum())
+    elif ha == 0:
+        d = point_segment(pa, b0, b1)
+    elif hb == 0:
+        d = point_segment(pb, a0, a1)
+    else:
+        d = segment_segment(a0, a1, b0, b1)
+    return d - (ra + rb)
+
+
+_SCENE = {}
+
+
+def degenerate_scene():
+    """(table, cases): world-fixed geometry on a 2-joint chain; cases = [(frame a, frame b, exact distance, witness_defined)],
+    every pair as (a, b) and as (b, a).  Computed once, shared, left unchanged.
+    Boxes (one turned, one aligned with the world axes, half extents 0.05 / 0.08 / 0.11) against a capsule (r 0.03, half length
+    0.07) or a sphere (r 0.04): generic; axis parallel to a face; axis parallel to an edge, beside the edge; nearest point a vertex;
+    an end point nearest to a face; spheres in front of a face, an edge and a vertex; a sphere centre inside the box.
+    Capsule pairs: parallel beside each other and staggered; tilted by 1e-3, 1e-6 and 1e-8 rad (both sides of the device's
+    denominator test) about the common perpendicular and within the common plane; collinear end to end; crossing axes (distance
+    -(ra + rb), normal undefined); a sphere (half length 0) beside and beyond the end of a capsule."""
+    if _SCENE:
+        return _SCENE["case"]
+    t = rt.chain_table(2, seed=1)
+    half = (0.05, 0.08, 0.11)
+    cases = []
+
+    def put(name, base, Rl, pl, **kw):
+        nonlocal t
+        Rb, pb = base[:9].reshape(3, 3), base[9:]
+        t = t.with_geometry(name, -1, rt.se3(Rb @ Rl, pb + Rb @ np.asarray(pl, dtype=float)), **kw)
+        return name
+
+    cap, sph = dict(radius=0.03, halflen=0.07), dict(radius=0.04)
+    I3 = np.eye(3)
+    for bname, base in (("boxT", rt.se3(rt.rpy(0.4, -0.7, 1.1), [0.5, 0.2, 0.3])), ("boxA", rt.se3(None, [-0.4, 0.6, 0.1]))):
+        put(bname, rt.se3(), base[:9].reshape(3, 3), base[9:], box=half)
+        others = [
+            put(bname + "_generic", base, rt.rpy(0.9, 0.5, -0.3), [0.25, 0.2, -0.18], **cap),
+            put(bname + "_face", base, rt.rpy(0.6, 0.0, 0.0), [0.16, 0.01, 0.02], **cap),          # axis in the plane x = 0.16
+            put(bname + "_edge", base, I3, [0.10, 0.12, 0.03], **cap),                             # axis along z beside the edge x, y
+            put(bname + "_vertex", base, rt.rpy(0.0, 0.9, 0.7), [0.2, 0.22, 0.27], **cap),
+            put(bname + "_end", base, rt.rpy(0.0, np.pi / 2, 0.0), [0.2, 0.02, -0.03], **cap),     # axis along x, towards the face
+            put(bname + "_sphere_face", base, I3, [0.01, -0.2, 0.03], **sph),
+            put(bname + "_sphere_edge", base, I3, [0.12, 0.0, -0.2], **sph),
+            put(bname + "_sphere_vertex", base, I3, [-0.1, -0.15, 0.2], **sph),
+            put(bname + "_sphere_inside", base, I3, [0.02, -0.05, 0.03], **sph),
+        ]
+        cases += [(bname, o, o != bname + "_sphere_inside") for o in others]
+    baseC = rt.se3(rt.rpy(-0.5, 0.8, 0.2), [0.1, -0.5, 0.4])
+    put("capA", baseC, I3, [0.0, 0.0, 0.0], **cap)
+    others = [(put("cap_parallel", baseC, I3, [0.1, 0.0, 0.05], **cap), True),
+              (put("cap_staggered", baseC, I3, [0.05, 0.0, 0.3], **cap), True),
+              (put("cap_collinear", baseC, I3, [0.0, 0.0, 0.3], **cap), True),
+              (put("cap_crossing", baseC, rt.rpy(np.pi / 2, 0.0, 0.0), [0.0, 0.01, 0.02], **cap), False),
+              (put("sphere_beside", baseC, I3, [0.0, 0.12, 0.03], **sph), True),
+              (put("sphere_beyond", baseC, I3, [0.0, 0.0, 0.2], **sph), True)]
+    for eps in (1e-3, 1e-6, 1e-8):
+        others.append((put(f"cap_tilt_perp_{eps:g}", baseC, rt.rpy(eps, 0.0, 0.0), [0.1, 0.0, 0.02], **cap), True))
+        others.append((put(f"cap_tilt_plane_{eps:g}", baseC, rt.rpy(eps, 0.0, 0.0), [0.0, 0.1, 0.02], **cap), True))
+    cases += [("capA", o, sep) for o, sep in others]
+    out = []
+    for a, b, witness in cases:
+        for x, y in ((a, b), (b, a)):
+            out.append((x, y, float(exact_distance(t, t.frame_id(x), t.frame_id(y))), witness))
+    _SCENE["case"] = (t, out)
+    return _SCENE["case"]
+
+
 # ------------------------------------------------------------------------------------------------------------ checker
 def checker_distance(t, pair, q):
     """The CPU checker's distance of one pair at q [n][nv]: a problem with this pair as its only constraint row, orc_node_constraints
@@ -241,3 +375,35 @@ def test_wrapper_refuses_bad_arguments_before_any_gpu_work(monkeypatch):
         with pytest.raises(ValueError, match="q: expected shape"):
             h.clearance([("cap1", "cap3")], q=bad)
 
+
+def test_segment_box_on_hand_made_cases():
+    h = (1.0, 2.0, 3.0)
+    assert segment_box((4, 0, 0), (4, 0, 0), h) == 3.0                        # a point in front of a face
+    assert segment_box((4, 6, 0), (4, 6, 0), h) == 5.0                        # ... of an edge
+    assert segment_box((3, 4, 4), (3, 4, 4), h) == 3.0                        # ... of a vertex (2, 2, 1)
+    assert segment_box((5, -9, 1), (5, 9, 1), h) == 4.0                       # parallel to a face
+    assert segment_box((4, 6, -9), (4, 6, 9), h) == 5.0                       # parallel to an edge
+    assert segment_box((9, 0, 0), (3, 0, 0), h) == 2.0                        # an end point
+    assert segment_box((4, 0, 0), (0, 4, 0), h) == np.sqrt(LD(0.5))           # passes the edge (1, 2, .) at 45 degrees: |(1, 2) - (1.5, 2.5)|
+    assert segment_box((-9, 0, 0), (9, 0, 0), h) == 0.0                       # through the box
+    assert segment_box((0.5, 0, 0), (0.5, 0, 0), h) == 0.0
+
+
+def test_checker_matches_the_exact_reference_on_box_and_degenerate_capsule_pairs():
+    """Every pair of degenerate_scene, both orders, within 1e-12 of the longdouble reference (the bound of the device test)."""
+    t, cases = degenerate_scene()
+    assert len(cases) == 2 * (2 * 9 + 12)
+    q = np.zeros((1, t.nv))
+    worst = 0.0
+    bad = []
+    for a, b, want, _ in cases:
+        got = checker_distance(t, (a, b), q)[0]
+        worst = max(worst, abs(got - want))
+        print(f"{a} / {b}: checker {got:.17g} exact {want:.17g} diff {got - want:.2e}")
+        if not abs(got - want) <= 1e-12:
+            bad.append((a, b, got, want))
+    assert not bad, bad
+    inside = [w for a, b, w, _ in cases if "inside" in a + b]
+    crossing = [w for a, b, w, _ in cases if "crossing" in a + b]
+    assert all(w < -0.04 for w in inside) and all(abs(w + 0.06) < 1e-15 for w in crossing)
+    assert sum(w > 0 for _, _, w, _ in cases) == len(cases) - len(inside) - len(crossing)

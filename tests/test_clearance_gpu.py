@@ -2,7 +2,8 @@
 "Diagnostics"): distances, witness points and the minimum of any pair list at the iterate or at given configurations.
 
 References: the CPU checker (every pair, boxes included) and the numpy closed forms of tests/test_clearance.py (spheres and
-capsules; pinned to the checker there).  1e-12 absolute on distances throughout: the tolerance
+capsules; pinned to the checker there), and for box pairs and degenerate capsule pairs the exact longdouble reference of
+tests/test_clearance.py::degenerate_scene.  1e-12 absolute on distances throughout: the tolerance
 tests/test_many_collision_costs.py uses for the distance of a pair row."""
 import ctypes as C
 
@@ -367,3 +368,35 @@ def test_class_surface(hip_backend):
     assert np.abs(d - tc.reference(table, model_pairs, states[:, :7])).max() <= TOL
     with pytest.raises(ValueError, match="states"):
         ocp.clearance(states[:, :5])
+
+
+
+def test_box_and_degenerate_capsule_pairs_against_the_exact_reference(hip_backend):
+    """The 60 pairs of tc.degenerate_scene (box against capsule and sphere: generic, parallel to a face, parallel to an edge,
+    vertex, end point, sphere centre inside; capsules parallel, tilted by 1e-3 / 1e-6 / 1e-8 rad, collinear, crossing, against a
+    sphere), each as (a, b) and (b, a), through clearance(q=..., witness=True): distance to 1e-12 of the longdouble value; where
+    the pair is separated pa - pb = d n, |n| = 1 and both witness points lie on their surfaces.  With crossing axes and with the
+    sphere centre inside the box only the distance is asserted (the normal is not defined)."""
+    t, cases = tc.degenerate_scene()
+    pairs = [(a, b) for a, b, _, _ in cases]
+    want = np.array([w for _, _, w, _ in cases])
+    q = np.zeros((B, 2, t.nv))
+    h = _handle(hip_backend, t)
+    d, wit = h.clearance(pairs, q=q, witness=True)
+    h.close()
+    assert d.shape == (B, 2, len(pairs))
+    err = np.abs(d - want).max((0, 1))
+    for (a, b), e, w in zip(pairs, err, want):
+        print(f"{a} / {b}: exact {w:.17g} err {e:.2e}")
+    assert err.max() <= TOL, [(p, e) for p, e in zip(pairs, err) if e > TOL]
+    pa, pb, n = wit[..., 0, :], wit[..., 1, :], wit[..., 2, :]
+    for k, (a, b, w, witness) in enumerate(cases):
+        if not witness:
+            continue
+        assert w > 0.0
+        gap = np.abs(pa[..., k, :] - pb[..., k, :] - d[..., k, None] * n[..., k, :]).max()
+        norm = np.abs(np.sqrt((n[..., k, :] ** 2).sum(-1)) - 1.0).max()
+        sa = tc.surface_distance(t, t.frame_id(a), q, pa[..., k, :]).max()
+        sb = tc.surface_distance(t, t.frame_id(b), q, pb[..., k, :]).max()
+        print(f"{a} / {b}: pa - pb - d n {gap:.2e} | |n| - 1 | {norm:.2e} surfaces {sa:.2e} {sb:.2e}")
+        assert gap <= TOL and norm <= 1e-14 and sa <= TOL and sb <= TOL, (a, b, gap, norm, sa, sb)
