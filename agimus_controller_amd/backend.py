@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = [
     "agx_traj_stream_joins", "agx_traj_stream_timing", "agx_ocp_set_obstacle_placements",
     "agx_ocp_set_first_pack", "agx_ocp_first_pack_counts", "agx_ocp_handoff_counts",
     "agx_ocp_iter_log", "agx_ocp_iter_log_read", "agx_ocp_item_costs", "agx_ocp_carry_counts", "agx_ocp_general_rows",
-    "agx_ocp_clearance",
+    "agx_ocp_clearance", "agx_ocp_last_direction", "agx_ocp_set_step_tail",
 ]  # fmt: skip
 
 
@@ -529,6 +529,24 @@ class HipOcp:
         kkt = np.empty(self.B)
         _chk(lib().agx_ocp_direction(self._h, _p(K), _p(k), _p(dx), _p(du), _p(kkt)))
         return K, k, dx, du, kkt
+
+    def set_step_tail(self, on: bool = True):
+        """k_step_tail (default) or forward pass, node KKT pass and head of the step as three launches; from the next solve on."""
+        _chk(lib().agx_ocp_set_step_tail(self._h, int(bool(on)), None))
+
+    def step_tail_launches(self) -> int:
+        """k_step_tail launches of this handle so far (0: its solves ran forward pass, node KKT pass and head as three launches)."""
+        n = C.c_longlong(0)
+        _chk(lib().agx_ocp_set_step_tail(self._h, -1, C.byref(n)))
+        return int(n.value)
+
+    def last_direction(self):
+        """dx, du and the node shares {kkt, cost, gap, violation} as the last SQP iteration of the last solve left them."""
+        dx = np.empty((self.B, self.T + 1, self.nx))
+        du = np.empty((self.B, self.T, self.nu))
+        nodestat = np.empty((self.B, self.T + 1, 4))
+        _chk(lib().agx_ocp_last_direction(self._h, _p(dx), _p(du), _p(nodestat)))
+        return dx, du, nodestat
 
     def time_kernel(self, which: int, reps: int) -> float:
         ms = C.c_double()

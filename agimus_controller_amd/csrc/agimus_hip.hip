@@ -436,7 +436,12 @@ int launch_riccati(agx_ocp *o, int forward, bool pair = false, int iter = 0, con
       return 0;
     }
     if constexpr (NV <= 7) {
-      if (pair && o->riccati_mx)
+      // `forward` is honoured by the one-wave MFMA-layout pair only (solve_resident with the step tail: the forward pass runs in
+      // k_step_tail); k_riccati_pair and the segmented pair above run their forward pass whatever it says, as they always did
+      if (pair && o->riccati_mx && !forward)
+        hipLaunchKernelGGL((agx::k_riccati_mx_pair_sweeps<NV>), dim3(16 * ((o->B + 7) / 8)), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt,
+                           o->d_aux, o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_Kout, o->d_state, iter);
+      else if (pair && o->riccati_mx)
         hipLaunchKernelGGL((agx::k_riccati_mx_pair<NV>), dim3(16 * ((o->B + 7) / 8)), dim3(64), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_aux,
                            o->d_Kws, o->d_kws, o->d_dx, o->d_w, o->d_Kout, o->d_state, iter);
       else if (pair)
@@ -511,6 +516,31 @@ int launch_step(agx_ocp *o, int iter, int max_iter, int mode, bool with_node_kkt
                          pack ? first_block(o) : nullptr, o->first_stride);
     HIPCHK(hipGetLastError());
     return 0;
+  });
+}
+
+// Forward pass, K3 and the head of the step in one launch, one workgroup per instance (k_step_tail, agx_step_tail.hpp), behind a
+// sweep launched with forward = 0: the 7-joint capacity, unconstrained, no general rows, one-wave MFMA-layout sweeps.
+bool step_tail_path(const agx_ocp *o) {
+  return o->step_tail && o->nv <= 7 && !o->has_con && !o->general && o->riccati_mx && o->node_kkt_wide && o->mx2_S < 2;
+}
+int launch_step_tail(agx_ocp *o, int iter, int max_iter, unsigned long long seq, bool pack) {
+  if (o->T + 1 > 512) return fail("step kernel supports horizons up to 511 nodes");
+  return dispatch(o->nv, o->chain, [&](auto NVc, auto CHc) -> int {
+    constexpr int NV = decltype(NVc)::value;
+    (void)CHc;
+    if constexpr (NV <= 7) {
+      double *xs_t = o->d_xs + (size_t)o->B * (o->T + 1) * o->nx, *us_t = o->d_us + (size_t)o->B * o->T * o->nu;
+      hipLaunchKernelGGL((agx::k_step_tail<NV>), dim3(o->B), dim3(agx::kTailThreads), 0, o->stream, o->d_ocp, o->d_dt, o->d_qt, o->d_aux,
+                         o->d_Kws, o->d_kws, o->d_xs, o->d_us, o->d_dx, o->d_w, o->d_du, xs_t, us_t, o->d_nodestat, o->d_state, iter,
+                         max_iter, o->d_ndone, host_words(o, false, seq), o->d_Kout, pack ? first_block(o) : nullptr, o->first_stride);
+      HIPCHK(hipGetLastError());
+      o->step_tail_launches += 1;
+      return 0;
+    } else {
+      (void)iter; (void)max_iter; (void)seq; (void)pack;
+      return fail("the step tail serves the 7-joint capacity");
+    }
   });
 }
 
@@ -966,6 +996,7 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
   // Every iteration after the first finds its tiles already there (the accepted trial of the line search left them); a
   // derivative pass of its own is needed at the start and after an iteration that ended with every step length rejected.
   bool need_k1 = true;
+  const bool tail = step_tail_path(o);  // the sweep leaves its forward pass to the launch that also holds K3 and the head
   // the exit fix-up of the gains is launched only if an instance can have finished (or the loop can
   // have ended) in an iteration whose direction sweep was not paired with the gains sweep
   bool need_fixup = false;
@@ -993,14 +1024,15 @@ int solve_resident(agx_ocp *o, int max_iter, double max_time, bool prologue_done
     if (o->has_con && o->admm_prefactor && o->riccati_mx && o->nv <= 7 && !o->general) {
       if (admm_direction(o, true)) return -1;  // LQR pass inside, next to the ADMM factorisation
     } else {
-      if (launch_riccati(o, 1, pair, it)) return -1;
+      if (launch_riccati(o, tail ? 0 : 1, pair, it)) return -1;
       if (o->has_con && admm_direction(o)) return -1;
     }
     if (prof_mark(o, 1, false)) return -1;
     const bool last = it + 1 == max_iter;
     if (prof_mark(o, 2, true)) return -1;
     const unsigned long long seq_head = ++o->seq;
-    if (launch_step(o, it, max_iter, 1, !o->has_con, true, seq_head, pair && packing)) return -1;
+    if (tail ? launch_step_tail(o, it, max_iter, seq_head, pair && packing)
+             : launch_step(o, it, max_iter, 1, !o->has_con, true, seq_head, pair && packing)) return -1;
     if (prof_mark(o, 2, false)) return -1;
     if (iter_log_mark(o, it, 0)) return -1;  // the evaluation and how the head left every instance, before a trial round moves on
     // Large batches, from the second iteration on (where warm-started MPC steps converge): what the head left, to the host
@@ -2260,6 +2292,24 @@ int agx_ocp_direction(agx_ocp *o, double *K, double *k, double *dx, double *du, 
   HIPCHK(hipMemcpyAsync(hs.data(), o->d_state, sizeof(DevState) * B, hipMemcpyDeviceToHost, o->stream));
   HIPCHK(hipStreamSynchronize(o->stream));
   if (kkt) for (size_t b = 0; b < B; ++b) kkt[b] = hs[b].kkt;
+  return 0;
+}
+
+int agx_ocp_set_step_tail(agx_ocp *o, int on, long long *launches) {
+  if (!o) return fail("null handle");
+  if (on >= 0) o->step_tail = on != 0;  // (read at every solve: step_tail_path)
+  if (launches) *launches = o->step_tail_launches;
+  return 0;
+}
+
+int agx_ocp_last_direction(agx_ocp *o, double *dx, double *du, double *nodestat) {
+  if (!o) return fail("null handle");
+  if (set_device(o)) return -1;
+  const size_t B = o->B, T = o->T;
+  if (dx && down(o, dx, o->d_dx, B * (T + 1), 2)) return -1;
+  if (du && down(o, du, o->d_du, B * T, 1)) return -1;
+  if (nodestat) HIPCHK(hipMemcpyAsync(nodestat, o->d_nodestat, sizeof(double) * B * (T + 1) * 4, hipMemcpyDeviceToHost, o->stream));
+  HIPCHK(hipStreamSynchronize(o->stream));
   return 0;
 }
 

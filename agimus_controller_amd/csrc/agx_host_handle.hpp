@@ -144,6 +144,8 @@ struct agx_ocp {
   double *d_mx2_elem = nullptr, *d_mx2_bnd = nullptr, *d_mx2_cl = nullptr;  // [2][B][S][3][256] segment elements, [2][B][S][256] boundary value functions, [B][S][256] transitions under the gains
   bool k1_fused = true;     // AGX_K1_FUSED=0: running and terminal nodes of the derivative pass as two launches (profiling)
   bool node_kkt_wide = true;  // AGX_NODE_KKT_WIDE=0: nv <= 7 node shares by k_node_kkt (a wait per group of loads) instead of k_node_kkt_ahead
+  long long step_tail_launches = 0;  // k_step_tail launches of this handle so far (agx_ocp_set_step_tail reports it)
+  bool step_tail = true;      // agx_ocp_set_step_tail(0): forward pass in the sweep, K3 and the head of the step as three launches instead of k_step_tail
   // Tile carry across MPC steps: the running-node tiles live in a ring (tile_slot, agx_kernels.hpp) whose
   // origin advances with every carried agx_ocp_mpc_step, so that the first derivative pass of a step evaluates nodes 0, T - 1
   // and T only.  7-joint capacity, eight-lane derivative kernel, unconstrained, MFMA-layout sweeps, one dt for every node.

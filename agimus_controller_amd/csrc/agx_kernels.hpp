@@ -497,10 +497,18 @@ __device__ __forceinline__ double fast_rcp(double x) {
 // twice -- indexed by the lane's column (operand of the products) and by its row (the update).
 // Per node: two FMAs, a DPP row reduction (w = -kw - Kw dx), the lane-local state update and one
 // transposing broadcast of the new state (row r's value to every lane of column r).
-template <int NV>
+// TAP (k_step_tail, agx_step_tail.hpp): what the pass leaves for the other waves of its workgroup next to the stores below --
+// the start state, every node's (w[t], dx[t + 1]) from the lanes that store them, and how many nodes are complete, after each
+// group of the pipelined loop.  The default does nothing and leaves the kernels that call the pass without one as they were.
+struct FwdNoTap {
+  __device__ __forceinline__ void start(int) const {}
+  __device__ __forceinline__ void node(int, int, double, double, double) const {}
+  __device__ __forceinline__ void done_to(int) const {}
+};
+template <int NV, class TAP = FwdNoTap>
 __device__ __forceinline__ void riccati_forward(const DevOcp &o, const int b, const int T, const double *__restrict__ dts, const double *__restrict__ qb,
                                                 const double *__restrict__ Kw, const double *__restrict__ kw,
-                                                double *__restrict__ dxs, double *__restrict__ wss, const double *s_dt) {
+                                                double *__restrict__ dxs, double *__restrict__ wss, const double *s_dt, const TAP tap = TAP()) {
   constexpr int NX = 2 * NV, TS = QT<NV>::SIZE;
   typedef QT<NV> Q;
   const int lane = threadIdx.x;
@@ -510,6 +518,7 @@ __device__ __forceinline__ void riccati_forward(const DevOcp &o, const int b, co
   const double inm = in ? 1.0 : 0.0;
   double *dx = dxs + (long long)b * (T + 1) * NX, *ws = wss + (long long)b * T * NV;
   if (lane < NV) { dx[lane] = 0.0; dx[NV + lane] = 0.0; }
+  tap.start(lane);
   __threadfence_block();  // the gains written by the backward sweep are read back by other lanes below
   double dq_r = 0.0, dv_r = 0.0, dq_c = 0.0, dv_c = 0.0;
   struct Gain { double kq, kv, kw, fq, fv; };
@@ -542,6 +551,7 @@ __device__ __forceinline__ void riccati_forward(const DevOcp &o, const int b, co
       ws[(long long)t * NV + r] = wv;
       dx[(long long)(t + 1) * NX + r] = nq;
       dx[(long long)(t + 1) * NX + NV + r] = nv2;
+      tap.node(t, r, wv, nq, nv2);
     }
     // refill this register set FWD_DEPTH nodes ahead: after the last use of its old contents and unconditionally
     // (the last node again at the end) -- see the note on the loop latch in agx_riccati_mx.hpp
@@ -555,6 +565,7 @@ __device__ __forceinline__ void riccati_forward(const DevOcp &o, const int b, co
     Gain g1;
     load_gain(g1, t);
     fstep(g1, t);
+    tap.done_to(t + 1);
   }
   if (t < T) {
     Gain g[FWD_DEPTH];
@@ -564,6 +575,7 @@ __device__ __forceinline__ void riccati_forward(const DevOcp &o, const int b, co
     for (; t < T; t += FWD_DEPTH) {
 #pragma unroll
       for (int i = 0; i < FWD_DEPTH; ++i) fstep(g[i], t + i);
+      tap.done_to(t + FWD_DEPTH);
     }
   }
 }
@@ -1338,6 +1350,10 @@ __global__ void __launch_bounds__(128) k_sqp_accept(const DevOcp *__restrict__ o
     write_trial_iterate<NV>(o, b, s_alpha, xs, us, dxs, dus, xs_t, us_t);
   }
 }
+
+}  // namespace agx
+#include "agx_step_tail.hpp"  // forward pass, K3 and the head above in one launch per instance (default for the 7-joint capacity)
+namespace agx {
 
 // ---------------------------------------------------------------------------
 // small utilities

@@ -417,6 +417,15 @@ int agx_ocp_calc_diff(agx_ocp *ocp, double *tiles);
  * Riccati backward + linear forward, KKT, reported gains): K [B][T][nu][ndx], k = acceleration-space
  * feed-forward [B][T][nu], dx [B][T+1][ndx], du [B][T][nu], kkt [B].                                */
 int agx_ocp_direction(agx_ocp *ocp, double *K, double *k, double *dx, double *du, double *kkt);
+/* What the last SQP iteration of the last solve left on the device, copied out as it stands (nothing is launched): the
+ * direction dx [B][T+1][ndx], du [B][T][nu] and the node shares nodestat [B][T+1][4] = {kkt, cost, gap, violation} the head of
+ * the step summed.  Any pointer may be NULL.  Entries of instances that had finished before that iteration are older.       */
+int agx_ocp_last_direction(agx_ocp *ocp, double *dx, double *du, double *nodestat);
+/* Forward pass, node KKT pass and head of the step of an SQP iteration as one launch per instance (k_step_tail; default on,
+ * where it applies: 7-joint capacity, unconstrained, no general rows, one-wave sweeps) or, on = 0, as the three launches it
+ * replaces; on < 0 leaves the choice as it is.  Same bits either way (tests/test_step_tail_gpu.py); takes effect from the next
+ * solve.  *launches (may be NULL): k_step_tail launches of this handle so far -- whether its solves took the path at all.  */
+int agx_ocp_set_step_tail(agx_ocp *ocp, int on, long long *launches);
 /* The QP tiles of the node-parallel derivative pass at the resident (xs, us) exactly as the solver's sweep reads
  * them (acceleration-input form): qt [B][T+1][*qt_size], aux [B][T+1][*aux_size] (either may be
  * NULL; the sizes are always returned).  Layout per node, blocks nv x LD row major with LD = 8 (nv <= 8) or 32:
